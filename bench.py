@@ -15,11 +15,16 @@ frames, the DDPM-1000 reverse loop, the flow-warp decode of the round's
 tc + tp frames; then (N > 1) the RCCL all-gather of the generated videos.
   * `--warmup W`: W untimed graph replays (a W-step reverse loop, plus one
     untimed encoder / decoder pass that builds every native handle);
-  * `--steps K`: the timed region is ceil(K / steps_per_generation) >= 1
-    COMPLETE generations — a partial generation would not deliver frames —
-    so the reported `steps` is the number of reverse-diffusion steps actually
-    timed (2000 per generation) and `ms_per_step` = timed wall / steps.
-`value` = predicted frames delivered / timed wall (max over ranks).
+  * `--steps K`: the timed region is exactly K reverse-diffusion steps, run in
+    the order the eval driver runs them: whole generations first (2000 steps
+    each for BAIR), then the leading K mod 2000 steps of the next generation
+    (its rounds' encoder, reverse loop and — for a round that completes — decode;
+    the loop of the last round stops after the K-th step). The default is one
+    generation. `steps` = K and `ms_per_step` = timed wall / K.
+`value` = predicted frames / timed wall (max over ranks), a generation's frames
+counted in proportion to the steps timed: frames_per_generation * K /
+steps_per_generation / wall. For whole generations that is the frames delivered
+over the wall time; for a part of one it is the rate the timed steps sustain.
 
 Multi-GPU: `--gpus N` without a torch.distributed launcher spawns N child ranks
 (one process per GPU, LOCAL_RANK = GPU index) before any GPU call; under
@@ -35,12 +40,23 @@ Other BASELINE workloads: `--config {kth,cityscapes,ucf,smmnist}` (WORKLOADS bel
 each dataset's tc / tp / rounds / sampler, its wrapper and denoiser variant, a per-GPU
 batch), one bench line each; BAIR stays the default the driver runs.
 
-Output: rank 0 prints (and flushes) a JSON line as soon as the timed region and
-the roofline launch timing are done, marked "partial": true, then the complete
-line with `cpu_baseline` once the CPU port has been timed. The last line is the
-result.
+A plain run sets up, warms up, times the steps and prints one JSON result line.
+`--dump-outputs DIR` also writes what the last timed step delivered as
+DIR/<name>.npy (float32): `videos`, the gathered clips of the last generation,
+when the timed steps end on a whole generation, else `latent`, the reverse
+loop's x after the K-th step. An array over 48 MB is cut to a fixed, seeded
+choice of its clips (dump_sample). Inputs, weights and noise are seeded, so two
+runs with the same arguments deliver the same arrays.
+
+`--full` adds the measurements that take runs of their own: the per-kernel
+roofline (launch timing of the hot-path kernels) and, on one GPU, the CPU
+baseline (the oracle port timed on the host cores). Rank 0 then prints (and
+flushes) a JSON line as soon as the timed region and the roofline launch timing
+are done, marked "partial": true, then the complete line with `cpu_baseline`
+once the CPU port has been timed. The last line is the result.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--config NAME]
+                       [--dump-outputs DIR] [--full]
 """
 import argparse
 import json
@@ -150,19 +166,24 @@ def parse(argv=None):
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help='torch.distributed backend for N > 1 (gloo: test the rank path on one GPU)')
     ap.add_argument('--steps', type=int, default=None,
-                    help='reverse-diffusion steps to time, rounded up to whole generations (default: one)')
+                    help='reverse-diffusion steps to time (default: one generation)')
     ap.add_argument('--warmup', type=int, default=5, help='untimed graph replays')
     ap.add_argument('--batch', type=int, default=None, help='clips per GPU (default: the workload\'s)')
     ap.add_argument('--sampling-steps', type=int, default=None,
                     help='default: the workload\'s sampler (BAIR: DDPM-1000, the metric); fewer = DDIM-S sweeps')
     ap.add_argument('--total-pred', type=int, default=None)
     ap.add_argument('--tp', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also time the per-kernel roofline and the CPU baseline')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step delivered as DIR/<name>.npy (float32)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--cpu-steps', type=int, default=5, help='timed oracle steps per CPU batch point')
     ap.add_argument('--precision', default=None, choices=['fp32', 'f16x3', 'bf16_attn'],
                     help='conv / attention arithmetic (include/extdm.h EXTDM_PRECISION_*); default: package default')
-    ap.add_argument('--no-roofline', action='store_true', help='test-only: skip the per-kernel roofline timing')
-    ap.add_argument('--dump', default=None, help='test-only: save the gathered videos of the last generation here')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the per-kernel roofline timing')
+    ap.add_argument('--dump', default=None,
+                    help='test-only: save the gathered videos of the last generation here (whole generations only)')
     ap.add_argument('--stub', action='store_true',
                     help='test-only: CPU/gloo stand-in workload that exercises the launcher and rank plumbing')
     a = ap.parse_args(argv)
@@ -283,7 +304,46 @@ def metric_label(config, meta_metric, sampler, name, tc, total_pred, baseline):
             f'not the headline metric')
 
 
-class NativeWorkload:
+DUMP_BYTES = 48 * 2 ** 20  # per dumped array (one array per run; the dump stays under 64 MB)
+
+
+def dump_sample(a):
+    """`a` (clips first) as float32, whole while it fits DUMP_BYTES; else the clips of a fixed
+    choice (PCG64 seed 0, without replacement, in ascending order) that fit, and for a single clip
+    past the budget its leading elements. Depends on the array's shape alone."""
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.nbytes <= DUMP_BYTES:
+        return a
+    per_clip = a[0].nbytes
+    if per_clip > DUMP_BYTES:
+        return a[0].reshape(-1)[:DUMP_BYTES // 4].copy()
+    rows = np.random.Generator(np.random.PCG64(0)).choice(a.shape[0], size=DUMP_BYTES // per_clip, replace=False)
+    return a[np.sort(rows)]
+
+
+def dump_outputs(out, path):
+    os.makedirs(path, exist_ok=True)
+    for name, t in out.items():
+        np.save(os.path.join(path, name + '.npy'), dump_sample(t.detach().cpu().numpy()))
+
+
+class Workload:
+    """The step accounting both workloads share: K timed steps = K // steps_per_generation whole
+    generations, then the leading K % steps_per_generation steps of the next one."""
+
+    def run_steps(self, K):
+        """{name: array gathered on rank 0 (None on the others)} of what the K-th step delivered:
+        'videos' after a whole generation, 'latent' inside one."""
+        gens, rest = divmod(K, self.steps_per_generation)
+        out = None
+        for g in range(gens):
+            out = {'videos': self.generation(g)}
+        if rest:
+            out = self.partial_generation(gens, rest)
+        return out
+
+
+class NativeWorkload(Workload):
     """The product path: FlowDiffusion + autoregressive_sample on the HIP library, for one of
     the BASELINE workloads (WORKLOADS[args.config])."""
 
@@ -332,11 +392,46 @@ class NativeWorkload:
                                              seed=1234 + idx, sample_base=self.start)
         return self.pkg.dist.gather_shards(out.contiguous(), self.world * self.args.batch, self.world)
 
+    @torch.no_grad()
+    def partial_generation(self, idx, n):
+        """The leading n < steps_per_generation reverse steps of generation idx, as
+        autoregressive_sample runs them (same seed, noise keys and sampler calls): per round the
+        encoder, the reverse loop, and the decode that feeds the next round; the last round's loop
+        stops after the n-th step and its x is returned as {'latent': x} (gathered like the
+        videos). n = steps_per_generation returns {'videos': ...}, equal to generation(idx)'s."""
+        pkg, fd, d = self.pkg, self.fd, self.fd.diffusion
+        T = d.num_timesteps
+        if d.is_ddim_sampling:
+            pairs = pkg.ddim_time_pairs(T, d.sampling_timesteps)
+            sampler, eta, times, nxt = pkg._lib.SAMPLER_DDIM, d.ddim_sampling_eta, [p[0] for p in pairs], [p[1] for p in pairs]
+        else:
+            sampler, eta, times, nxt = pkg._lib.SAMPLER_DDPM, 0., list(reversed(range(T))), None
+        cur = self.clips[:, :, :self.tc].contiguous()
+        B = cur.shape[0]
+        preds = []
+        while n > 0 and len(preds) < self.rounds:
+            ret, x_cond, fea, ref = fd.encode(cur)
+            k = min(n, len(times))
+            x = torch.empty(B, 3, self.tp, x_cond.shape[3], x_cond.shape[4], device=self.dev)
+            d._run_sampler(B, self.dev, fea.shape[-1], lambda h: h.sample(
+                sampler, times[:k], nxt and nxt[:k], eta, x_cond.float().contiguous(), fea.float().contiguous(), x,
+                seed=1234 + idx, sample_base=self.start, round_idx=len(preds), use_graph=d.use_graph))
+            n -= k
+            if k == len(times):
+                out = fd.decode(ret, x, ref)['sample_out_vid']
+                preds.append(out[:, :, -self.tp:])
+                cur = out[:, :, -self.tc:].contiguous()
+        if len(preds) == self.rounds:  # n covered the generation (the tests' cross-check)
+            vid = torch.cat([self.clips[:, :, :self.tc], torch.cat(preds, dim=2)[:, :, :self.args.total_pred]], dim=2)
+            return {'videos': pkg.dist.gather_shards(vid.contiguous(), self.world * B, self.world)}
+        return {'latent': pkg.dist.gather_shards(x, self.world * B, self.world)}
+
     def sync(self):
         torch.cuda.synchronize()
 
     def check(self, out):
-        assert out.shape[0] == self.world * self.args.batch and torch.isfinite(out).all()
+        for v in out.values():
+            assert v.shape[0] == self.world * self.args.batch and torch.isfinite(v).all()
 
     def describe(self):
         a, B, w = self.args, self.args.batch, self.w
@@ -541,10 +636,10 @@ def lib_sha16():
         return None
 
 
-class StubWorkload:
+class StubWorkload(Workload):
     """CPU stand-in for tests (tests/test_bench_launcher.py): same rank plumbing
-    (shard, gloo all-gather, max-over-ranks), a result that depends only on the
-    global sample index, no GPU."""
+    (shard, gloo all-gather, max-over-ranks) and step accounting, a result that
+    depends only on the global sample index, no GPU."""
 
     def __init__(self, args, dev, world, rank):
         import importlib
@@ -559,17 +654,22 @@ class StubWorkload:
         pass
 
     def generation(self, idx):
+        return self.partial_generation(idx, self.steps_per_generation)['videos']
+
+    def partial_generation(self, idx, n):
         ids = torch.arange(self.start, self.start + self.count, dtype=torch.float32)
         out = ids.view(-1, 1, 1).expand(-1, 3, 2).contiguous()
-        time.sleep(0.05)
-        return self.D.gather_shards(out, self.world * self.args.batch, self.world)
+        time.sleep(0.0125 * n)
+        name = 'videos' if n == self.steps_per_generation else 'latent'
+        return {name: self.D.gather_shards(out, self.world * self.args.batch, self.world)}
 
     def sync(self):
         pass
 
     def check(self, out):
         n = self.world * self.args.batch
-        assert torch.equal(out[:, 0, 0], torch.arange(n, dtype=torch.float32))
+        for v in out.values():
+            assert torch.equal(v[:, 0, 0], torch.arange(n, dtype=torch.float32))
 
     def describe(self):
         return {'dtype': 'fp32', 'data': 'stub', 'config': {'workload': 'stub', 'global_batch': self.world *
@@ -739,24 +839,29 @@ def run_rank(args):
         wl = NativeWorkload(args, dev, world, rank)
     D = importlib_dist()
     wl.prime(args.warmup)
-    gens = max(1, math.ceil((args.steps or 1) / wl.steps_per_generation))
+    steps = wl.steps_per_generation if args.steps is None else args.steps
+    if steps < 1:
+        raise SystemExit('--steps must be at least 1')
+    if args.dump and steps % wl.steps_per_generation:
+        raise SystemExit('--dump saves a generation\'s videos: --steps must end on a whole generation')
+    gens = steps / wl.steps_per_generation
     if world > 1:
         dist.barrier()
     wl.sync()
     t0 = time.perf_counter()
-    for g in range(gens):
-        out = wl.generation(g)
+    out = wl.run_steps(steps)
     wl.sync()
     if world > 1:
         dist.barrier()
     el = D.max_over_ranks(time.perf_counter() - t0, device=dev if args.dist_backend == 'nccl' else None)
-    steps = gens * wl.steps_per_generation
     value = wl.frames_per_generation * gens / el
     result = None
     if rank == 0:
         wl.check(out)
+        if args.dump_outputs:
+            dump_outputs(out, args.dump_outputs)
         if args.dump:
-            torch.save(out.detach().cpu(), args.dump)
+            torch.save(out['videos'].detach().cpu(), args.dump)
         meta = json.load(open(os.path.join(REPO, 'BASELINE.json')))
         T_ = wl.fd.diffusion.num_timesteps if hasattr(wl, 'fd') else 0
         sampler_ = f'DDPM {T_}' if args.sampling_steps >= T_ else f'DDIM {args.sampling_steps}'
@@ -767,16 +872,17 @@ def run_rank(args):
                   'steps': steps, 'warmup': args.warmup, 'ms_per_step': round(el / steps * 1e3, 4),
                   'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None}
         result.update(wl.describe())
-        result['generations'] = gens
-        result['requested_steps'] = args.steps if args.steps is not None else wl.steps_per_generation
+        result['generations'] = int(gens) if gens == int(gens) else round(gens, 6)
+        result['requested_steps'] = steps
         result['timed_s'] = round(el, 3)
-        result['roofline'] = None if args.no_roofline else wl.roofline()
-        result['partial'] = True
-        print(json.dumps(result), flush=True)
+        if args.full:
+            result['roofline'] = None if args.no_roofline else wl.roofline()
+            result['partial'] = True
+            print(json.dumps(result), flush=True)
     if world > 1:
         dist.barrier()  # the other ranks stay up until rank 0 has printed
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             result['cpu_baseline'] = wl.cpu_baseline()
         result['partial'] = False
         print(json.dumps(result), flush=True)

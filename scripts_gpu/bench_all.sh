@@ -6,6 +6,7 @@ TAG=${TAG:-r05}
 ( while sleep 45; do echo "heartbeat $(date +%T)" >> gpurun_out/${TAG}_bench_heartbeat.log; done ) &
 HB=$!
 trap 'kill $HB' EXIT
+EXTRA="--full ${EXTRA}"  # the roofline and the CPU baseline are legs of bench.py --full
 for c in ${CONFIGS:-bair smmnist kth ucf cityscapes}; do
   timeout -k 10 ${TL:-700} python -u bench.py --config $c ${EXTRA} > gpurun_out/${TAG}_bench_$c.json 2> gpurun_out/${TAG}_bench_$c.err
   rc=$?; echo "$c rc=$rc"

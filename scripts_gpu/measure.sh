@@ -18,10 +18,13 @@ if [ -z "$SKIP_PMC" ]; then
   for c in kth cityscapes ucf smmnist; do CONFIG=$c LAYERS=6 bash scripts_gpu/pmc_layers.sh || exit 1; done
 fi
 if [ -z "$SKIP_PROF" ]; then
-  rm -rf gpurun_out/prof_$TAG
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_$TAG -o run --output-format csv -- python bench.py --sampling-steps 20 --steps 1 --warmup 1 --no-cpu-baseline > gpurun_out/prof_$TAG.log 2>&1
-  rc=$?; echo "rocprof rc=$rc"; tail -2 gpurun_out/prof_$TAG.log; [ $rc -ne 0 ] && exit $rc
-  cp "$(find gpurun_out/prof_$TAG -name '*kernel_stats.csv' | head -1)" gpurun_out/${TAG}_bair_ddim20_kernel_stats.csv
-  for p in attn_x3_kernel cross_attn_x3p conv_x3_kernel xpath_x3 sampler; do python scripts_gpu/kernel_launches.py gpurun_out/prof_$TAG $p; done > gpurun_out/${TAG}_bair_ddim20_launches.txt
-  find gpurun_out/prof_$TAG -name "*kernel_trace.csv" -delete
+  OUT=${OUT:-bench_out}; mkdir -p $OUT  # step 2 writes here
+  P=$OUT/prof_$TAG
+  rm -rf $P
+  # no --steps: one whole generation (2 rounds x 20 steps), with the roofline's launches as before
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats -d $P -o run --output-format csv -- python bench.py --sampling-steps 20 --warmup 1 --full --no-cpu-baseline > $P.log 2>&1
+  rc=$?; echo "rocprof rc=$rc"; tail -2 $P.log; [ $rc -ne 0 ] && exit $rc
+  cp "$(find $P -name '*kernel_stats.csv' | head -1)" $OUT/${TAG}_bair_ddim20_kernel_stats.csv
+  for p in attn_x3_kernel cross_attn_x3p conv_x3_kernel xpath_x3 sampler; do python scripts_gpu/kernel_launches.py $P $p; done > $OUT/${TAG}_bair_ddim20_launches.txt
+  find $P -name "*kernel_trace.csv" -delete
 fi

@@ -27,6 +27,28 @@ def _run(tmp_path, gpus, batch, tag):
     return json.loads(lines[-1]), torch.load(dump, weights_only=True)
 
 
+def test_partial_generation_follows_the_generation():
+    """`--steps K` inside a generation (NativeWorkload.partial_generation) issues the calls
+    autoregressive_sample issues: over all of a generation's steps it returns the same videos bit
+    for bit; stopped earlier it returns the reverse loop's x, the same on every call and
+    moving with every step."""
+    import bench
+    args = bench.parse(['--batch', '2', '--sampling-steps', '4'])
+    w = bench.NativeWorkload(args, torch.device('cuda', 0), 1, 0)
+    w.prime(1)
+    assert w.steps_per_generation == 8
+    whole = w.run_steps(8)
+    again = w.partial_generation(0, 8)
+    assert list(whole) == list(again) == ['videos']
+    assert whole['videos'].shape == (2, 3, 2 + 28, 64, 64)
+    assert torch.equal(whole['videos'], again['videos'])
+    a, b, c = w.run_steps(6), w.run_steps(6), w.run_steps(5)  # round 0 and 2 (1) steps of round 1
+    assert list(a) == list(c) == ['latent'] and a['latent'].shape == (2, 3, 14, 32, 32)
+    assert torch.isfinite(a['latent']).all()
+    assert torch.equal(a['latent'], b['latent']) and not torch.equal(a['latent'], c['latent'])
+    torch.cuda.synchronize()
+
+
 def test_two_gloo_ranks_equal_one_rank(tmp_path):
     r1, v1 = _run(tmp_path, 1, 4, 'one')
     r2, v2 = _run(tmp_path, 2, 2, 'two')
