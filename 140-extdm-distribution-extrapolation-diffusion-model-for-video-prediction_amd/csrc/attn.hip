@@ -11,6 +11,11 @@
 //                    V^T comes from an LDS transpose of the V tile)
 //   The cyclic shift, zero padding and window partition/reverse are index maps:
 //   tokens are gathered from and scattered back to their original positions.
+// temporal_attention64: the fp32 temporal attention of clips of 33..64 frames (and of any
+//   shorter clip), dim_head 16 or 32, on VALU FMAs: lane = query frame, one wave per head, the
+//   head's rotated K and V in LDS, read as broadcasts; the scores are computed twice (row
+//   maximum, then exp / sum / PV), so nothing is kept per key. Not a hot path: EXTDM_PRECISION_FP32
+//   and the C = 512 level of wo_ref. A lane's loads are H*W floats apart (one line each).
 // cross_attention: TrajWarp multi-head cross-attention (u12:719-773),
 //   flash-style over 32-key chunks with an online softmax (the reference
 //   materialises the 8x3584x512 map; its outputs are the same up to rounding).
@@ -155,6 +160,69 @@ __global__ __launch_bounds__(256) void window_attn_kernel(const float* __restric
   }
 }
 
+template <int DH>
+__global__ __launch_bounds__(128) void temporal_attn64_kernel(const float* __restrict__ qkv, long qsb, long qsc,
+                                                              float* __restrict__ o, long osb, long osc, int D, int HW,
+                                                              int heads, const float* __restrict__ bias /*[heads][64][64]*/,
+                                                              const float* __restrict__ rcos,
+                                                              const float* __restrict__ rsin, float q_scale,
+                                                              long plane /* T stride = H*W */) {
+  __shared__ float Ks[2][64][DH + 1], Vs[2][64][DH + 1];
+  const int t = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int b = blockIdx.x / HW, hw = blockIdx.x % HW;
+  const bool valid = t < D;
+  const long pos = (long)t * plane + hw;
+  const int hid = heads * DH;
+  const float* qb = qkv + (long)b * qsb;
+  for (int hd = wave; hd < heads; hd += 2) {
+    float q[DH];
+#pragma unroll
+    for (int d = 0; d < DH; d += 2) {
+      // scale, then rotary on the interleaved pair (d, d + 1) at position t
+      const float c = rcos[t * (DH / 2) + (d >> 1)], sn = rsin[t * (DH / 2) + (d >> 1)];
+      const float q0 = (valid ? qb[(long)(hd * DH + d) * qsc + pos] : 0.f) * q_scale;
+      const float q1 = (valid ? qb[(long)(hd * DH + d + 1) * qsc + pos] : 0.f) * q_scale;
+      const float k0 = valid ? qb[(long)(hid + hd * DH + d) * qsc + pos] : 0.f;
+      const float k1 = valid ? qb[(long)(hid + hd * DH + d + 1) * qsc + pos] : 0.f;
+      q[d] = q0 * c + (-q1) * sn;
+      q[d + 1] = q1 * c + q0 * sn;
+      Ks[wave][t][d] = k0 * c + (-k1) * sn;
+      Ks[wave][t][d + 1] = k1 * c + k0 * sn;
+      Vs[wave][t][d] = valid ? qb[(long)(2 * hid + hd * DH + d) * qsc + pos] : 0.f;
+      Vs[wave][t][d + 1] = valid ? qb[(long)(2 * hid + hd * DH + d + 1) * qsc + pos] : 0.f;
+    }
+    // Ks / Vs[wave] are private to the wave
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const float* bd = bias + ((long)hd * 64 + t) * 64;
+    auto score = [&](int j) {
+      float sv = 0.f;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) sv = fmaf(q[d], Ks[wave][j][d], sv);
+      return sv + bd[j];
+    };
+    float mx = -INFINITY;
+    for (int j = 0; j < D; ++j) mx = fmaxf(mx, score(j));
+    float acc[DH];
+#pragma unroll
+    for (int d = 0; d < DH; ++d) acc[d] = 0.f;
+    float sum = 0.f;
+    for (int j = 0; j < D; ++j) {
+      const float p = expf(score(j) - mx);
+      sum += p;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) acc[d] = fmaf(p, Vs[wave][j][d], acc[d]);
+    }
+    if (valid) {
+      float* ob = o + (long)b * osb + pos;
+#pragma unroll
+      for (int d = 0; d < DH; ++d) ob[(long)(hd * DH + d) * osc] = acc[d] / sum;
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // Ks / Vs reuse by the wave's next head
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
 __global__ __launch_bounds__(256) void cross_attn_kernel(const float* __restrict__ Q, const float* __restrict__ K,
                                                          const float* __restrict__ V, float* __restrict__ O, int C,
                                                          int heads, int NQ, int NK) {
@@ -245,6 +313,20 @@ void window_attention(hipStream_t s, const View& qkv, const View& o, const AttnG
   note_kernel("window_attn_kernel");
   hipLaunchKernelGGL(window_attn_kernel, dim3(nblocks), dim3(256), 0, s, qkv.p, qkv.sb, qkv.sc, o.p, o.sb, o.sc, g,
                      heads, bias_dense, rope_cos, rope_sin, q_scale, qkv.st);
+}
+
+bool temporal_attention64(hipStream_t s, const View& qkv, const View& o, const AttnGeom& g, int heads, int dim_head,
+                          const float* bias64, const float* rope_cos, const float* rope_sin, float q_scale) {
+  if (g.mode != 1 || g.D > 64 || (dim_head != 16 && dim_head != 32) || qkv.st != o.st) return false;
+  const unsigned nblocks = (unsigned)(qkv.B * g.H * g.W);
+  note_kernel("temporal_attn64_kernel<%d>", dim_head);
+  if (dim_head == 32)
+    hipLaunchKernelGGL(temporal_attn64_kernel<32>, dim3(nblocks), dim3(128), 0, s, qkv.p, qkv.sb, qkv.sc, o.p, o.sb,
+                       o.sc, g.D, g.H * g.W, heads, bias64, rope_cos, rope_sin, q_scale, qkv.st);
+  else
+    hipLaunchKernelGGL(temporal_attn64_kernel<16>, dim3(nblocks), dim3(128), 0, s, qkv.p, qkv.sb, qkv.sc, o.p, o.sb,
+                       o.sc, g.D, g.H * g.W, heads, bias64, rope_cos, rope_sin, q_scale, qkv.st);
+  return true;
 }
 
 void cross_attention(hipStream_t s, const float* q, const float* k, const float* v, float* o, int B, int C,

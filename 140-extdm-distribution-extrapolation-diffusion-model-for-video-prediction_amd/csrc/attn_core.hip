@@ -1,7 +1,7 @@
 // Attention core (the QK^T and PV contractions on qkv produced by a 1x1 conv) of
 //   STW window self-attention    WindowAttention3D + STWAttentionLayer, u12:408-559
 //                                (shifted 3-D windows of <= 64 tokens: ada / ada_u22 4x4x4)
-//   temporal attention per pixel Attention, u12:252-302 (<= 32 frames)
+//   temporal attention per pixel Attention, u12:252-302 (<= 64 frames)
 // in two arithmetics (template X3):
 //   X3 = true   f16x3 (hi / lo fp16 operands, three v_mfma_f32_32x32x16_f16 per product,
 //               fp32-faithful; conv_x3.hip): the F16X3 path for the shapes the fused
@@ -11,8 +11,9 @@
 // Everything around the core (LayerNorms, the qkv / proj 1x1 convs, residuals) runs as f16x3.
 //
 // One wave per (token group, head); a group is NT 32-token tiles: NT = 2 for 64-token
-// windows, NT = 1 for windows of <= 32 tokens and for temporal groups (32 / T' pixels'
-// frames, T' = 16 or 32 slots), so no block of the score matrix is wholly masked.
+// windows and for clips of 33..64 frames (one pixel's 64 frame slots), NT = 1 for windows of
+// <= 32 tokens and for temporal groups of <= 32 frames (32 / T' pixels' frames, T' = 16 or 32
+// slots), so no block of the score matrix is wholly masked.
 //   lane = (token column c = lane & 31, half h = lane >> 5); an operand fragment holds the
 //   8 dims 16s + 8h .. +7 of k-step s (dim_head 32: s = 0, 1; dim_head 16: s = 0 only, the
 //   ada denoiser's C = 256 windows), so rotary pairs stay in-lane. At dim_head 16 the O^T tile's
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(256) void attn_core_kernel(const float* __restrict_
   const int gidx = xcd ? (int)((blockIdx.x & 7) * (G8 >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
   if (gidx >= total_groups) return;
   const int b = gidx / groups_per_sample, grp = gidx % groups_per_sample;
-  const int per = g.D <= 16 ? 16 : 32;  // MODE 1: frame slots per pixel
+  const int per = NT == 2 ? 64 : (g.D <= 16 ? 16 : 32);  // MODE 1: frame slots per pixel
   TokB tq[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) tq[t] = token_b<MODE, NT>(32 * t + c, g, st, grp, per);
@@ -305,7 +306,8 @@ bool attention_core(hipStream_t s, const View& qkv, const View& o, const AttnGeo
                     const float* bias_dense, int bstride, const float* rope_cos, const float* rope_sin, float q_scale,
                     bool bf16) {
   if ((dim_head != 32 && dim_head != 16) || qkv.st != o.st) return false;
-  if (dim_head == 16 && (g.mode != 0 || bf16)) return false;  // dim 16: the ada C = 256 windows, f16x3
+  // dim 16, f16x3 only: the ada C = 256 windows, and the ada temporal layers beyond 32 frames
+  if (dim_head == 16 && (bf16 || (g.mode != 0 && g.D <= 32))) return false;
   int groups, nt = 1;
   if (g.mode == 0) {
     const int N = g.ws0 * g.ws1 * g.ws2;
@@ -313,9 +315,15 @@ bool attention_core(hipStream_t s, const View& qkv, const View& o, const AttnGeo
     nt = N > 32 ? 2 : 1;
     groups = (g.Dp / g.ws0) * (g.Hp / g.ws1) * (g.Wp / g.ws2);
   } else {
-    if (g.D > 32) return false;
-    const int ppw = 32 / (g.D <= 16 ? 16 : 32);  // pixels per 32-token group
-    groups = (g.H * g.W + ppw - 1) / ppw;
+    if (g.D > 64) return false;
+    if (g.D > 32) {  // one pixel per 64-slot group, bias_dense [heads][64][64]
+      if (bstride != 64) return false;
+      nt = 2;
+      groups = g.H * g.W;
+    } else {
+      const int ppw = 32 / (g.D <= 16 ? 16 : 32);  // pixels per 32-token group
+      groups = (g.H * g.W + ppw - 1) / ppw;
+    }
   }
   const int total = qkv.B * groups;
   int* flag = x3_range_ptr();
@@ -330,7 +338,11 @@ bool attention_core(hipStream_t s, const View& qkv, const View& o, const AttnGeo
                      qkv.st, o.p, o.sb, o.sc, g, heads, groups, total, bias_dense, bstride, rope_cos, rope_sin,    \
                      q_scale, flag, xcd);                                                                     \
   } while (0)
-  if (dim_head == 16) {
+  if (g.mode == 1 && nt == 2) {
+    if (dim_head == 16) CORE_GO(1, true, 2, 16);
+    else if (bf16) CORE_GO(1, false, 2, 32);
+    else CORE_GO(1, true, 2, 32);
+  } else if (dim_head == 16) {
     if (nt == 2) CORE_GO(0, true, 2, 16);
     else CORE_GO(0, true, 1, 16);
   } else if (g.mode == 0 && nt == 2) {

@@ -299,9 +299,11 @@ struct AttnGeom {
 // frame slots per pixel of the fused temporal attention (32 tokens per wave = 32 / per pixels)
 __host__ __device__ inline int temporal_slots(const AttnGeom& g) { return g.per ? g.per : (g.D <= 16 ? 16 : 32); }
 // Attention core (attn_core.hip): QK^T / softmax / PV over qkv [B][3*heads*32][T][H][W]
-// into o [B][heads*32][T][H][W], token groups of <= 64 (temporal: <= 32 frames),
-// dim_head 32; f16x3 (fp32-faithful) or bf16 (EXTDM_PRECISION_BF16_ATTN). False if the
-// shape is not covered. bias_dense [heads][bstride][bstride].
+// into o [B][heads*32][T][H][W], token groups of <= 64 (temporal: <= 32 frames at bstride 32,
+// 33..64 frames — one pixel per 64-slot group — at bstride 64), dim_head 32, or 16 in f16x3
+// (windows, and temporal groups of 33..64 frames); f16x3 (fp32-faithful) or bf16
+// (EXTDM_PRECISION_BF16_ATTN). False if the shape is not covered.
+// bias_dense [heads][bstride][bstride].
 bool attention_core(hipStream_t s, const View& qkv, const View& o, const AttnGeom& g, int heads, int dim_head,
                     const float* bias_dense, int bstride, const float* rope_cos, const float* rope_sin, float q_scale,
                     bool bf16);
@@ -310,6 +312,11 @@ bool attention_core(hipStream_t s, const View& qkv, const View& o, const AttnGeo
 void window_attention(hipStream_t s, const View& qkv, const View& o, const AttnGeom& g, int heads,
                       const float* bias_dense /*[heads][32][32]*/, const float* rope_cos,
                       const float* rope_sin /*[>=32][16]*/, float q_scale);
+// fp32 temporal attention of clips of up to 64 frames (attn.hip), dim_head 16 or 32, between the
+// same 1x1 convs; bias64 the T5 table [heads][64][64]; rope tables [64][dim_head/2]. False if the
+// shape is not covered.
+bool temporal_attention64(hipStream_t s, const View& qkv, const View& o, const AttnGeom& g, int heads, int dim_head,
+                          const float* bias64, const float* rope_cos, const float* rope_sin, float q_scale);
 // Shapes the fused attention kernels handle: heads 8, C in {64,128,256}, a group of
 // <= 32 or exactly 64 tokens, dim_head 16 or 32.
 bool fused_attn_supported(int C, int ntok, int dim_head, int heads);
@@ -345,6 +352,13 @@ bool stw64_x3(hipStream_t s, const View& x, const AttnGeom& g, int heads, int di
 bool temporal_x3(hipStream_t s, const View& x, const View& out, const AttnGeom& g, int heads, int dim_head,
                  const float* gamma, const float* ln_w, const float* ln_b, const void* wpk, const float* wsc,
                  const float* mbias, const float* rcos, const float* rsin, float q_scale, bool bf16);
+// The same layer for clips of 33..64 frames (temporal64_x3.hip): two waves per pixel, 64 frame
+// slots, C in {64, 128}, dim_head 16 or 32; the stw_x3 weight packing; mbias [8][64][64] (T5 bias,
+// -inf for key frames >= D, times 2^(e_q + e_k)); out shares x's strides and may alias x.
+bool temporal64_x3_supported(int C, int frames, int dim_head, int heads);
+bool temporal64_x3(hipStream_t s, const View& x, const View& out, const AttnGeom& g, int heads, int dim_head,
+                   const float* gamma, const float* ln_w, const float* ln_b, const void* wpk, const float* wsc,
+                   const float* mbias, const float* rcos, const float* rsin, float q_scale, bool bf16);
 // TrajWarp cross-attention (u12:719-773): q [B][256][NQ], k,v [B][256][NK].
 // f16x3 implicit-GEMM conv (conv_gemm_x3.hip): every mode / kernel size of conv_forward's
 // fp32 GEMM; false if the weight has no f16x3 GEMM packing

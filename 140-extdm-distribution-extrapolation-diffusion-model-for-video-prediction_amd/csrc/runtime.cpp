@@ -102,7 +102,8 @@ struct ExtdmHandle {
   float* rope_cos = nullptr;  // [32][16]
   float* rope_sin = nullptr;
   std::unordered_map<std::string, float*> bias_dense;  // STW layer prefix -> [heads][32][32]
-  float* time_bias = nullptr;                            // [heads][32][32]
+  float* time_bias = nullptr;                            // [heads][tb_stride][tb_stride]
+  int tb_stride = 32;                                    // 32, or 64 for clips of 33..64 frames
   // host copies for the f16x3 kernels' bias + mask tables (stw_mask_bias)
   std::unordered_map<std::string, std::pair<std::vector<float>, int>> bias_host;  // prefix -> (dense, stride)
   std::vector<float> time_bias_host;
@@ -993,6 +994,25 @@ struct ExtdmHandle {
     mask_bias[key] = {d, 1};
     return d;
   }
+  // The same for clips of 33..64 frames (temporal64_x3.hip): one pixel per 64-slot group,
+  // [heads][64 query frames][64 key frames] from the [heads][64][64] T5 table, -inf for key
+  // frames >= D
+  const float* temporal_mask_bias64(const AttnGeom& g, float s2) {
+    const std::string key = "temporal64|" + std::to_string(g.D) + "|" + std::to_string(std::ilogb(s2));
+    auto it = mask_bias.find(key);
+    if (it != mask_bias.end()) return it->second.first;
+    const int nh = cfg.heads;
+    REQUIRE(nh == 8 && g.D > 32 && g.D <= 64 && tb_stride == 64, "temporal 64-slot bias + mask table: shape");
+    std::vector<float> t((size_t)nh * 4096, 0.f);
+    for (int hd = 0; hd < nh; ++hd)
+      for (int i = 0; i < 64; ++i)
+        for (int j = 0; j < 64; ++j)
+          t[((size_t)hd * 64 + i) * 64 + j] = j >= g.D ? -INFINITY : time_bias_host[((size_t)hd * 64 + i) * 64 + j] * s2;
+    float* d = dmalloc(t.size() * 4);
+    HIPCHK(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    mask_bias[key] = {d, 1};
+    return d;
+  }
 
   // Packed weights of the fused attention kernels (stw_fused.hip header): qkv rows
   // in 32-row units (one head of dim 32 / two heads of dim 16).
@@ -1251,6 +1271,54 @@ struct ExtdmHandle {
     conv(x, o, nullptr, P(p + ".fn.fn.attn.proj.weight"), 1, 0, D(p + ".fn.fn.attn.proj.bias"), &x);
   }
 
+  // The same layer for clips of 33..64 frames: one pixel's frames fill a 64-slot group (two
+  // 32-token tiles), the T5 table is [heads][64][64]. F16X3 (and BF16_ATTN at dim_head 32): the
+  // fused kernel (temporal64_x3.hip) at C = 64 / 128 (EXTDM_NO_T64=1, or the flags of x3_attn_ok,
+  // send those to the next route: A/B), else the unfused core route (attn_core.hip MODE 1,
+  // NT = 2: C = 256). EXTDM_PRECISION_FP32, BF16_ATTN at dim_head 16 and EXTDM_NO_X3_CORE: the
+  // fp32 kernel (attn.hip temporal_attention64) between the same prologue and 1x1 convs.
+  void temporal_long(const std::string& p, const View& x, const View& out, AttnGeom g) {
+    const std::string a = p + ".fn.fn.fn";
+    const int T = x.T;
+    REQUIRE(T <= 64 && tb_stride == 64, "temporal attention over more than 64 frames");
+    g.per = 64;
+    const bool x3 = cfg.precision == EXTDM_PRECISION_F16X3 || (bf16_attn() && cfg.dim_head == 32);
+    auto flag = [](const char* n) { const char* v = getenv(n); return v && v[0] && v[0] != '0'; };
+    if (x3 && !flag("EXTDM_NO_T64") && !flag("EXTDM_NO_X3_ATTN") && !flag("EXTDM_NO_X3_TEMPORAL") &&
+        temporal64_x3_supported(x.C, T, cfg.dim_head, cfg.heads) && out.sb == x.sb && out.sc == x.sc && out.st == x.st &&
+        x.st == (long)x.H * x.W && ((long)(x.C - 1) * x.sc + (long)T * x.st) * 4 < (1L << 30)) {  // 31-bit buffer offsets per sample
+      const AttnX3W& w = packed_attn_x3(a + ".attn.to_qkv.weight", a + ".attn.to_out.weight", a + ".norm.weight",
+                                        a + ".norm.bias");
+      const float* mb = temporal_mask_bias64(g, w.s2);
+      if (plan) return;
+      REQUIRE(temporal64_x3(s, x, out, g, cfg.heads, cfg.dim_head, D(p + ".fn.norm.gamma"), D(a + ".norm.weight"),
+                            D(a + ".norm.bias"), w.w, w.sc, mb, rope_cos, rope_sin, q_scale(), bf16_attn()),
+              "f16x3 64-slot temporal attention launch rejected");
+      return;
+    }
+    static const bool off = [] { const char* v = getenv("EXTDM_NO_X3_CORE"); return v && v[0] && v[0] != '0'; }();
+    const bool core = bf16_attn() ? cfg.dim_head == 32 : (cfg.precision == EXTDM_PRECISION_F16X3 && !off);
+    last_core = core;
+    Scope sc(arena);
+    const int hid = cfg.heads * cfg.dim_head;
+    View z = alloc_cf(x.B, x.C, T, x.H, x.W), rr = alloc_cf(x.B, x.C, T, x.H, x.W);
+    if (!plan && bench_stage == 0)
+      temporal_prologue(s, x, D(p + ".fn.norm.gamma"), D(a + ".norm.weight"), D(a + ".norm.bias"), z, rr);
+    View qkv = alloc_cf(x.B, 3 * hid, T, x.H, x.W);
+    if (bench_stage == 0 || bench_stage == 2) conv(qkv, z, nullptr, P(a + ".attn.to_qkv.weight"), 1, 0, nullptr);
+    View o = alloc_cf(x.B, hid, T, x.H, x.W);
+    if (!plan && (bench_stage == 0 || bench_stage == 1)) {
+      if (core)
+        REQUIRE(attention_core(s, qkv, o, g, cfg.heads, cfg.dim_head, time_bias, 64, rope_cos, rope_sin, q_scale(),
+                               bf16_attn()),
+                "64-slot temporal attention core launch rejected");
+      else
+        REQUIRE(temporal_attention64(s, qkv, o, g, cfg.heads, cfg.dim_head, time_bias, rope_cos, rope_sin, q_scale()),
+                "fp32 64-frame temporal attention launch rejected");
+    }
+    if (bench_stage == 0 || bench_stage == 3) conv(out, o, nullptr, P(a + ".attn.to_out.weight"), 1, 0, nullptr, &rr);
+  }
+
   // Residual(PreNorm(dim, EinopsToAndFrom(AttentionLayer))) over the frames of every
   // pixel (u12:236-327, 903-915): out = x + chanLN(x) + to_out(attn(LN(chanLN(x)))).
   // out may alias x.
@@ -1263,6 +1331,7 @@ struct ExtdmHandle {
     // frames filled 14 of a wave's 32 tokens at 16 slots); EXTDM_X3_PER8=0: 16 / 32 only (A/B)
     static const bool per8 = [] { const char* v = getenv("EXTDM_X3_PER8"); return !(v && v[0] == '0'); }();
     g.per = T <= 8 && per8 ? 8 : (T <= 16 ? 16 : 32);
+    if (T > 32) { temporal_long(p, x, out, g); return; }
     const bool fused_x3 = x3_attn_ok(x.C, T, 1) && out.sc == x.sc && out.st == x.st;
     if (core_attn(T, 32, fused_x3, false)) {
       // double-LN prologue, f16x3 qkv conv, the core (bf16 or f16x3 MFMA), f16x3 to_out + residual
@@ -2115,8 +2184,10 @@ struct ExtdmHandle {
     {
       const HostTensor& emb = H("time_rel_pos_bias.relative_attention_bias.weight");
       const int nh = (int)emb.shape[1], T = frames();
-      REQUIRE(T <= 32, "temporal attention over more than 32 frames");
-      std::vector<float> d((size_t)nh * 1024, 0.f);
+      REQUIRE(T <= 64, "temporal attention over more than 64 frames");
+      // [heads][32][32] up to 32 frames, [heads][64][64] beyond (distances >= 32 clamp to bucket nb - 1)
+      const int st = tb_stride = T <= 32 ? 32 : 64;
+      std::vector<float> d((size_t)nh * st * st, 0.f);
       const int nb = 16, max_exact = 8;
       for (int i = 0; i < T; ++i)
         for (int j = 0; j < T; ++j) {
@@ -2133,7 +2204,7 @@ struct ExtdmHandle {
             large = std::min(large, nb - 1);
             bucket = ret + large;
           }
-          for (int h = 0; h < nh; ++h) d[(size_t)h * 1024 + i * 32 + j] = emb.f[(size_t)bucket * nh + h];
+          for (int h = 0; h < nh; ++h) d[((size_t)h * st + i) * st + j] = emb.f[(size_t)bucket * nh + h];
         }
       time_bias = dmalloc(d.size() * 4);
       HIPCHK(hipMemcpy(time_bias, d.data(), d.size() * 4, hipMemcpyHostToDevice));
@@ -2153,7 +2224,7 @@ struct ExtdmHandle {
     }
     REQUIRE(cfg.dim_head == 32 || cfg.dim_head == 16, "this build supports attn_dim_head 16 or 32");
     REQUIRE(cfg.arch != EXTDM_ARCH_WO_REF || cfg.tc >= 2, "wo_ref needs at least two cond frames");
-    REQUIRE(frames() <= 32, "temporal attention over more than 32 frames");
+    REQUIRE(frames() <= 64, "temporal attention over more than 64 frames (model frames = cond + pred, limit 64)");
     // small tensors (biases, norm gains) go to the device now so that no
     // host->device copy can happen while a sampler step is being captured
     for (auto& kv : host)

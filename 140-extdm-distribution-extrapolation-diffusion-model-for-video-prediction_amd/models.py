@@ -27,6 +27,9 @@ from .spec import (UnetConfig, unet_spec, GeneratorConfig, generator_spec, ARCH_
 from .weights import synth_state_dict
 
 
+MAX_FRAMES = 64  # model frames per clip: the 64-slot temporal attention (include/extdm.h)
+
+
 def _exists(x):
     return x is not None
 
@@ -85,6 +88,9 @@ class Unet3D(nn.Module):
         self.ucfg = UnetConfig(dim=dim, channels=channels, dim_mults=tuple(dim_mults), window=tuple(window_size),
                                heads=attn_heads, dim_head=attn_dim_head, tc=cond_num, tp=pred_num, latent=framesize,
                                fea_size=fea_size, arch=self.ARCH)
+        if self.ucfg.frames > MAX_FRAMES:
+            raise ValueError(f'{self.ucfg.frames} model frames (cond + pred; wo_ref: cond - 1 + pred): the temporal '
+                             f'attention kernels hold at most {MAX_FRAMES} frames per pixel (64-frame limit)')
         spec = unet_spec(self.ucfg)
         _register_tree(self, spec, synth_state_dict(spec, seed=seed, window=self.window_size))
         self._native = None

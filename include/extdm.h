@@ -31,6 +31,11 @@
  *                        loops of calculate_psnr2 / calculate_ssim2, valid.py:226-233)
  *                                                   metrics/calculate_psnr.py:6-15,
  *                                                   metrics/calculate_ssim.py:6-41
+ *
+ * Limits: a denoiser sees tc + tp model frames (WO_REF: tc - 1 + tp); the temporal attention
+ * holds one pixel's frames in at most 64 token slots, so extdm_finalize refuses more than 64
+ * model frames ("temporal attention over more than 64 frames"). Up to 32 frames run the
+ * 8 / 16 / 32-slot kernels, 33..64 frames (e.g. KTH 10 -> 40) the 64-slot ones.
  */
 #ifndef EXTDM_H
 #define EXTDM_H
@@ -74,7 +79,7 @@ typedef struct ExtdmConfig {
   int window[3];       /* (2, 4, 4) */
   int heads;           /* attn_heads (8) */
   int dim_head;        /* attn_dim_head (32) */
-  int tc, tp;          /* cond / pred frames */
+  int tc, tp;          /* cond / pred frames; tc + tp (WO_REF: tc - 1 + tp) <= 64 */
   int latent;          /* flow-latent H = W (32) */
   int fea_size;        /* cond_fea H = W (16) */
   int fea_ch;          /* cond_fea channels (256) */
