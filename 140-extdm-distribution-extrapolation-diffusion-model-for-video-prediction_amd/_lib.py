@@ -12,12 +12,17 @@ EXPORTS = ['extdm_create', 'extdm_destroy', 'extdm_last_error', 'extdm_load_weig
            'extdm_workspace_bytes', 'extdm_unet_forward', 'extdm_sample', 'extdm_sampler_step', 'extdm_record_thresholds', 'extdm_bench_layer', 'extdm_bench_layer_kernel',
            'extdm_decode', 'extdm_set_lfae', 'extdm_region_params', 'extdm_region_hw', 'extdm_bg_params',
            'extdm_flow_predict', 'extdm_flow_hw', 'extdm_bottleneck', 'extdm_range_flag',
-           'extdm_attn_layer', 'extdm_frame_metrics_workspace', 'extdm_frame_metrics', 'extdm_bilinear_frames']
+           'extdm_attn_layer', 'extdm_frame_metrics_workspace', 'extdm_frame_metrics', 'extdm_bilinear_frames',
+           'extdm_sampler_step_t', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum']
+# ... and the declared symbols whose names hold a digit: tests/test_abi.py scans the header for
+# lower-case names only, so they are listed apart (tests/test_teacher_cpu.py checks them)
+EXPORTS_DIGIT = ['extdm_x0_loss']
 
 BG_TYPES = {'zero': 0, 'shift': 1, 'affine': 2, 'perspective': 3}
 
 SAMPLER_DDPM = 0
 SAMPLER_DDIM = 1
+LOSS_TYPES = {'l1': 0, 'l2': 1}  # include/extdm.h EXTDM_LOSS_*
 
 # include/extdm.h EXTDM_PRECISION_*: arithmetic of the direct convolutions
 PRECISIONS = {'fp32': 0, 'f16x3': 1, 'bf16_attn': 2}
@@ -109,6 +114,18 @@ def load():
     lg = ctypes.c_long
     L.extdm_bilinear_frames.argtypes = [vp, i32, i32, i32, i32, i32, vp, lg, lg, lg, vp, lg, lg, lg, i32, i32, i32, vp]
     L.extdm_bilinear_frames.restype = i32
+    L.extdm_sampler_step_t.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
+    L.extdm_sampler_step_t.restype = i32
+    L.extdm_q_sample.argtypes = [vp, i32, vp, vp, vp, u64, i32, i32, vp, vp, vp]
+    L.extdm_q_sample.restype = i32
+    L.extdm_x0_loss.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    L.extdm_x0_loss.restype = i32
+    L.extdm_p_losses.argtypes = [vp, i32, vp, vp, vp, vp, vp, u64, i32, i32, i32, i32, vp, vp, vp]
+    L.extdm_p_losses.restype = i32
+    L.extdm_abs_diff_chunks.argtypes = [i32]
+    L.extdm_abs_diff_chunks.restype = i32
+    L.extdm_abs_diff_sum.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.extdm_abs_diff_sum.restype = i32
     _lib = L
     return L
 
@@ -158,6 +175,39 @@ def _require_device(*tensors):
             raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
         if not t.is_contiguous() or t.dtype.is_floating_point and t.dtype != __import__('torch').float32:
             raise RuntimeError('ExtDM HIP path needs contiguous float32 tensors')
+
+
+def _require_i64(*ts):
+    """The t vectors of the teacher-forced entry points: the library reads B int64 values."""
+    import torch
+    for t in ts:
+        if t is not None and t.dtype != torch.int64:
+            raise RuntimeError(f'ExtDM HIP path needs int64 timestep tensors, got {t.dtype}')
+
+
+def _require_f64(t, numel):
+    import torch
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous() or t.numel() < numel:
+        raise RuntimeError(f'ExtDM HIP path needs a contiguous float64 device tensor of at least {numel} elements')
+
+
+def abs_diff_sum(a, b):
+    """Per-sample sums of |a - b| over everything but dim 0 -> device float64 [B], fixed summation
+    order (extdm_abs_diff_sum)."""
+    import torch
+    _require_device(a, b)
+    if a.shape != b.shape or a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise ValueError('abs_diff_sum: two float32 tensors of one shape expected')
+    B = a.shape[0]
+    n = a.numel() // B
+    if n >= 2 ** 31:
+        raise ValueError('abs_diff_sum: at most 2^31 - 1 elements per sample')
+    L = load()
+    sums = torch.empty(B, device=a.device, dtype=torch.float64)
+    work = torch.empty(B * L.extdm_abs_diff_chunks(n), device=a.device, dtype=torch.float64)
+    with torch.cuda.device(a.device):
+        check(L.extdm_abs_diff_sum(_ptr(a), _ptr(b), B, n, _ptr(sums), _ptr(work), _stream()))
+    return sums
 
 
 class Handle:
@@ -250,6 +300,38 @@ class Handle:
         _require_device(x, eps, noise, thresh_out)
         check(load().extdm_sampler_step(self.h, x.shape[0], sampler, int(t), int(t_next), float(eta), _ptr(x),
                                         _ptr(eps), _ptr(noise), _ptr(thresh_out), _stream()))
+
+    # ---- teacher-forced evaluation step (include/extdm.h); every t is a device int64 [B] ----
+    def sampler_step_t(self, sampler, t, t_next, eta, x, eps, noise=None, thresh_out=None):
+        _require_device(x, eps, noise, thresh_out, t, t_next)
+        _require_i64(t, t_next)
+        check(load().extdm_sampler_step_t(self.h, x.shape[0], sampler, _ptr(t), _ptr(t_next), float(eta), _ptr(x),
+                                          _ptr(eps), _ptr(noise), _ptr(thresh_out), _stream()))
+
+    def q_sample(self, t, x0, x_t, noise=None, seed=0, sample_base=0, round_idx=0, noise_out=None):
+        _require_device(t, x0, x_t, noise, noise_out)
+        _require_i64(t)
+        check(load().extdm_q_sample(self.h, x0.shape[0], _ptr(t), _ptr(x0), _ptr(noise), ctypes.c_uint64(seed),
+                                    sample_base, round_idx, _ptr(noise_out), _ptr(x_t), _stream()))
+
+    def x0_loss(self, t, x_t, eps, noise, loss_type, clip_denoised, pred_x0, loss_sum, thresh_out=None):
+        """loss_sum: device float64 [B]."""
+        _require_device(t, x_t, eps, noise, pred_x0, thresh_out)
+        _require_i64(t)
+        _require_f64(loss_sum, x_t.shape[0])
+        check(load().extdm_x0_loss(self.h, x_t.shape[0], _ptr(t), _ptr(x_t), _ptr(eps), _ptr(noise),
+                                   LOSS_TYPES[loss_type], 1 if clip_denoised else 0, _ptr(pred_x0), _ptr(loss_sum),
+                                   _ptr(thresh_out), _stream()))
+
+    def p_losses(self, t, x_cond, x_start, cond_fea, loss_type, clip_denoised, pred_x0, loss_sum, noise=None, seed=0,
+                 sample_base=0, round_idx=0):
+        _require_device(t, x_cond, x_start, cond_fea, pred_x0, noise)
+        _require_i64(t)
+        _require_f64(loss_sum, x_start.shape[0])
+        check(load().extdm_p_losses(self.h, x_start.shape[0], _ptr(t), _ptr(x_cond), _ptr(x_start), _ptr(cond_fea),
+                                    _ptr(noise), ctypes.c_uint64(seed), sample_base, round_idx,
+                                    LOSS_TYPES[loss_type], 1 if clip_denoised else 0, _ptr(pred_x0), _ptr(loss_sum),
+                                    _stream()))
 
     def record_thresholds(self, buf):
         """Record every later sample() call's per-step thresholds into buf[k * B + b] (device

@@ -451,6 +451,22 @@ size_t sampler_sel_bytes(int B, int n);
 void sampler_step_mw(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs, int* step_ctr,
                      const float* noise, uint64_t seed, int sample_base, int round, int k_lo, int k_hi, float q_w,
                      float* thresh_out, unsigned* ws, int* t_next, int nsteps);
+// Per-sample-coefficient forms (sampler.hip): coefs[b] is sample b's StepCoef.
+// sampler_step_t: the multi-workgroup update with noise [B][n] indexed like step 0 of a shared-t call.
+void sampler_step_t(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs, const float* noise,
+                    int k_lo, int k_hi, float q_w, float* thresh_out, unsigned* ws);
+// x_t = qc[b].x x0 + qc[b].y noise (qc: sqrt_alphas_cumprod[t_b], sqrt_one_minus_alphas_cumprod[t_b]);
+// noise null: Philox stream of (seed, sample_base + b, round), written to noise_out when non-null.
+void q_sample(hipStream_t s, float* xt, const float* x0, const float* noise, float* noise_out, int B, int n,
+              const float2* qc, uint64_t seed, int sample_base, int round);
+// pred_x0 = thresholded (clip) or raw x0 from (x_t, eps); loss_sum[b] = sum |noise - eps| (loss_type 0)
+// or sum (10 noise - 10 eps)^2 (1) in fp64. part: B x loss_chunks(n) doubles of scratch.
+int loss_chunks(int n);
+void x0_loss(hipStream_t s, const float* xt, const float* eps, const float* noise, int B, int n, const StepCoef* coefs,
+             int loss_type, bool clip, int k_lo, int k_hi, float q_w, float* pred_x0, double* part, double* loss_sum,
+             float* thresh_out, unsigned* ws);
+// sums[b] = sum |a[b] - b[b]| over n elements in fp64, fixed order (part as above)
+void abs_diff_sum(hipStream_t s, const float* a, const float* b, int B, int n, double* part, double* sums);
 void fill_normal(hipStream_t s, float* x, int B, int n, uint64_t seed, int sample_base, int round, int stream_id);
 void set_t_from_step(hipStream_t s, int* t_batch, int B, const StepCoef* coefs, const int* step_ctr);
 void incr_counter(hipStream_t s, int* ctr);

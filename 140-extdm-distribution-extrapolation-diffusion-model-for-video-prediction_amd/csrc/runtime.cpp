@@ -130,6 +130,13 @@ struct ExtdmHandle {
   StepCoef* coefs = nullptr;
   int coefs_cap = 0;
   float* eps_buf = nullptr;
+  // teacher-forced step (extdm_q_sample / extdm_x0_loss / extdm_p_losses / extdm_sampler_step_t):
+  // per-sample q_sample coefficients, loss partials [max_batch][loss_chunks(n)], and extdm_p_losses'
+  // x_t / drawn-noise buffers ([max_batch][n] each, allocated with the rest in finalize_workspace)
+  float2* qs_coefs = nullptr;
+  double* loss_part = nullptr;
+  float* xt_buf = nullptr;
+  float* noise_buf = nullptr;
   hipStream_t work = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
 
@@ -2274,6 +2281,12 @@ struct ExtdmHandle {
     t_batch = reinterpret_cast<int*>(dmalloc((size_t)std::max(B, 1) * sizeof(int)));
     step_ctr = reinterpret_cast<int*>(dmalloc(sizeof(int) * 4));
     sel = reinterpret_cast<unsigned*>(dmalloc(sampler_sel_bytes(std::max(B, 1), (int)n)));
+    qs_coefs = reinterpret_cast<float2*>(dmalloc((size_t)std::max(B, 1) * sizeof(float2)));
+    loss_part = reinterpret_cast<double*>(dmalloc((size_t)std::max(B, 1) * std::max(1, loss_chunks((int)n)) * sizeof(double)));
+    if (has_unet()) {
+      xt_buf = dmalloc((size_t)B * n * sizeof(float));
+      noise_buf = dmalloc((size_t)B * n * sizeof(float));
+    }
     HIPCHK(hipStreamCreateWithFlags(&work, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&ev_in, hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&ev_out, hipEventDisableTiming));
@@ -2318,6 +2331,28 @@ struct ExtdmHandle {
       c.use_noise = t_next > 0 ? 1 : 0;
     }
     return c;
+  }
+
+  // The per-sample tables of a device t vector (int64 [B]): with `step`, coefs[b] = make_coef(t_b[,
+  // t_next_b]); with `qs`, qs_coefs[b] = (sqrt_alphas_cumprod[t_b], sqrt_one_minus_alphas_cumprod[t_b]).
+  // Reads t back (synchronises `st`) so that the fp32 expressions stay the host's.
+  void coefs_from_t(hipStream_t st, int B, int sampler, const int64_t* t, const int64_t* t_next, float eta, bool step,
+                    bool qs) {
+    std::vector<int64_t> ht(B), hn(B, 0);
+    HIPCHK(hipMemcpyAsync(ht.data(), t, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    if (t_next) HIPCHK(hipMemcpyAsync(hn.data(), t_next, (size_t)B * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipStreamSynchronize(st));
+    if (step) ensure_coefs(B);
+    std::vector<StepCoef> cs(B);
+    std::vector<float2> qc(B);
+    for (int b = 0; b < B; ++b) {
+      REQUIRE(ht[b] >= 0 && ht[b] < cfg.timesteps && hn[b] >= 0 && hn[b] < cfg.timesteps, "t outside [0, timesteps)");
+      if (step) cs[b] = make_coef(sampler, (int)ht[b], (int)hn[b], eta);
+      if (qs) qc[b] = make_float2(H("sqrt_alphas_cumprod").f.at(ht[b]), H("sqrt_one_minus_alphas_cumprod").f.at(ht[b]));
+    }
+    if (step) HIPCHK(hipMemcpyAsync(coefs, cs.data(), (size_t)B * sizeof(StepCoef), hipMemcpyHostToDevice, st));
+    if (qs) HIPCHK(hipMemcpyAsync(qs_coefs, qc.data(), (size_t)B * sizeof(float2), hipMemcpyHostToDevice, st));
+    HIPCHK(hipStreamSynchronize(st));  // the host vectors are temporaries
   }
 
   void quantile_ranks(int n, int& klo, int& khi, float& w) const {
@@ -2492,6 +2527,103 @@ int extdm_sampler_step(ExtdmHandle* h, int B, int sampler, int t, int t_next, fl
       sampler_step(s, x, eps, B, n, h->coefs, h->step_ctr, noise, 0, 0, 0, klo, khi, w, thresh_out);
     }
     HIPCHK(hipStreamSynchronize(s));  // `c` is a host temporary
+  });
+}
+
+int extdm_sampler_step_t(ExtdmHandle* h, int B, int sampler, const int64_t* t, const int64_t* t_next, float eta,
+                         float* x, const float* eps, const float* noise, float* thresh_out, void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "handle not finalized");
+    REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(t && x && eps, "sampler_step_t: null pointer");
+    REQUIRE(sampler == EXTDM_SAMPLER_DDPM || t_next, "sampler_step_t: DDIM needs t_next");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    h->coefs_from_t(s, B, sampler, t, sampler == EXTDM_SAMPLER_DDIM ? t_next : nullptr, eta, true, false);
+    const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    int klo, khi;
+    float w;
+    h->quantile_ranks(n, klo, khi, w);
+    sampler_step_t(s, x, eps, B, n, h->coefs, noise, klo, khi, w, thresh_out, h->sel);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_q_sample(ExtdmHandle* h, int B, const int64_t* t, const float* x0, const float* noise, uint64_t seed,
+                   int sample_base, int round, float* noise_out, float* x_t, void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "handle not finalized");
+    REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(t && x0 && x_t, "q_sample: null pointer");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    h->coefs_from_t(s, B, EXTDM_SAMPLER_DDPM, t, nullptr, 0.f, false, true);
+    const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    q_sample(s, x_t, x0, noise, noise_out, B, n, h->qs_coefs, seed, sample_base, round);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_x0_loss(ExtdmHandle* h, int B, const int64_t* t, const float* x_t, const float* eps, const float* noise,
+                  int loss_type, int clip_denoised, float* pred_x0, double* loss_sum, float* thresh_out,
+                  void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "handle not finalized");
+    REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(t && x_t && eps && noise && pred_x0 && loss_sum, "x0_loss: null pointer");
+    REQUIRE(loss_type == EXTDM_LOSS_L1 || loss_type == EXTDM_LOSS_L2, "x0_loss: loss_type must be EXTDM_LOSS_L1 or _L2");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    h->coefs_from_t(s, B, EXTDM_SAMPLER_DDPM, t, nullptr, 0.f, true, false);
+    const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    int klo, khi;
+    float w;
+    h->quantile_ranks(n, klo, khi, w);
+    x0_loss(s, x_t, eps, noise, B, n, h->coefs, loss_type, clip_denoised != 0, klo, khi, w, pred_x0, h->loss_part,
+            loss_sum, thresh_out, h->sel);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_p_losses(ExtdmHandle* h, int B, const int64_t* t, const float* x_cond, const float* x_start,
+                   const float* cond_fea, const float* noise, uint64_t seed, int sample_base, int round, int loss_type,
+                   int clip_denoised, float* pred_x0, double* loss_sum, void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "handle not finalized");
+    REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(t && x_cond && x_start && cond_fea && pred_x0 && loss_sum, "p_losses: null pointer");
+    REQUIRE(h->xt_buf && h->noise_buf, "p_losses: the handle holds no denoiser");
+    REQUIRE(loss_type == EXTDM_LOSS_L1 || loss_type == EXTDM_LOSS_L2, "p_losses: loss_type must be EXTDM_LOSS_L1 or _L2");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    h->s = s;
+    h->bench_stage = 0;
+    const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    h->coefs_from_t(s, B, EXTDM_SAMPLER_DDPM, t, nullptr, 0.f, true, true);
+    q_sample(s, h->xt_buf, x_start, noise, noise ? nullptr : h->noise_buf, B, n, h->qs_coefs, seed, sample_base, round);
+    if (h->x3_convs()) x3_range_reset(s);
+    t_to_int(s, t, h->t_batch, B);
+    h->unet_forward(B, h->xt_buf, x_cond, cond_fea, h->eps_buf);
+    int klo, khi;
+    float w;
+    h->quantile_ranks(n, klo, khi, w);
+    x0_loss(s, h->xt_buf, h->eps_buf, noise ? noise : h->noise_buf, B, n, h->coefs, loss_type, clip_denoised != 0, klo,
+            khi, w, pred_x0, h->loss_part, loss_sum, nullptr, h->sel);
+    HIPCHK(hipGetLastError());
+    REQUIRE(!h->x3_convs() || x3_range_read(s) == 0,
+            "f16x3 precision: a conv input reached |v| >= 65504 during p_losses; results are not fp32-accurate "
+            "(create the handle with EXTDM_PRECISION_FP32)");
+  });
+}
+
+int extdm_abs_diff_chunks(int n) { return n > 0 ? loss_chunks(n) : 0; }
+
+int extdm_abs_diff_sum(const float* a, const float* b, int B, int n, double* sums, double* work, void* stream) {
+  return guarded([&] {
+    REQUIRE(a && b && sums && work, "abs_diff_sum: null pointer");
+    REQUIRE(B >= 1 && B <= 65535 && n >= 1, "abs_diff_sum: bad geometry");
+    abs_diff_sum(reinterpret_cast<hipStream_t>(stream), a, b, B, n, work, sums);
+    HIPCHK(hipGetLastError());
   });
 }
 

@@ -239,7 +239,9 @@ __device__ void sel_state(unsigned* ws, const SelLayout& L, int b, int sl, unsig
     *reinterpret_cast<uint4*>(ws + L.state(PASS, b, sl)) = make_uint4(prefix, mask, rank, 0u);
 }
 
-template <int PASS>
+// PS (per-sample coefficients, the teacher-forced / mixed-t entry points): coefs[b] instead of
+// coefs[*step_ctr]; step_ctr is not read.
+template <int PASS, bool PS>
 __global__ __launch_bounds__(SNT) void radix_count_kernel(const float* x, const float* eps, int n,
                                                           const StepCoef* coefs, const int* step_ctr,
                                                           unsigned* ws, int k_lo, int k_hi) {
@@ -247,8 +249,7 @@ __global__ __launch_bounds__(SNT) void radix_count_kernel(const float* x, const 
   __shared__ unsigned st[2][2];  // [sel][prefix, mask]
   const SelLayout L{(int)gridDim.y, (int)gridDim.x};
   const int b = blockIdx.y, ch = blockIdx.x;
-  const int step = *step_ctr;
-  const StepCoef c = coefs[step];
+  const StepCoef c = coefs[PS ? b : *step_ctr];
   const int nsel = k_hi == k_lo ? 1 : 2;
   for (int i = threadIdx.x; i < 512; i += SNT) lh[i >> 8][i & 255] = 0;
   if (threadIdx.x < 64 * nsel) {
@@ -278,6 +279,9 @@ __global__ __launch_bounds__(SNT) void radix_count_kernel(const float* x, const 
   }
 }
 
+// PS: the update of sample b with coefs[b]; noise and the Philox stream are indexed as step 0 of a
+// shared-t call (extdm_sampler_step), so a sample's result does not depend on which form ran it.
+template <bool PS>
 __global__ __launch_bounds__(SNT) void sampler_final_kernel(float* x, const float* eps, int n, const StepCoef* coefs,
                                                             const int* step_ctr, const float* noise, int B,
                                                             uint64_t seed, int sample_base, int round, int k_lo,
@@ -285,8 +289,8 @@ __global__ __launch_bounds__(SNT) void sampler_final_kernel(float* x, const floa
   __shared__ float vs[2];
   const SelLayout L{(int)gridDim.y, (int)gridDim.x};
   const int b = blockIdx.y;
-  const int step = *step_ctr;
-  const StepCoef c = coefs[step];
+  const int step = PS ? 0 : *step_ctr;
+  const StepCoef c = coefs[PS ? b : step];
   const int nsel = k_hi == k_lo ? 1 : 2;
   if (threadIdx.x < 64 * nsel) {
     const int sl = threadIdx.x >> 6;
@@ -344,6 +348,162 @@ __global__ __launch_bounds__(SNT) void sampler_final_kernel(float* x, const floa
       xb[e] = update(xb[e], eb[e], z);
     }
   }
+}
+
+// ---- teacher-forced evaluation step (Diffusion.py:276-319) ----
+// Every kernel below runs over (SCH-element chunk, sample) workgroups and gives thread i the
+// elements e0 + 4 i + 1024 k + {0..3} of its chunk whether or not the 16-byte path is taken, so a
+// per-thread fp64 sum adds the same terms in the same order for any pointer alignment.
+constexpr int Q_SAMPLE_STREAM = 0x7FFFFFFE;  // Philox "step" of q_sample's noise (x_T: 0x7FFFFFFF, steps: 0..S-1)
+
+__device__ __forceinline__ bool vec4_ok(int n, const void* a, const void* b, const void* c, const void* d) {
+  return (n & 3) == 0 && ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) |
+                           reinterpret_cast<uintptr_t>(c) | reinterpret_cast<uintptr_t>(d)) & 15) == 0;
+}
+__device__ __forceinline__ void load4(const float* p, int e, int e1, bool vec, float v[4]) {
+  if (vec) {
+    const float4 q = *reinterpret_cast<const float4*>(p + e);
+    v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = e + j < e1 ? p[e + j] : 0.f;
+  }
+}
+__device__ __forceinline__ void store4(float* p, int e, int e1, bool vec, const float v[4]) {
+  if (vec) {
+    *reinterpret_cast<float4*>(p + e) = make_float4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e + j < e1) p[e + j] = v[j];
+  }
+}
+
+// The workgroup's sum of the per-thread fp64 values in a fixed tree order; thread 0 returns it.
+__device__ __forceinline__ double block_sum_fixed(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = SNT / 2; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+// x_t[b] = qc[b].x * x0[b] + qc[b].y * noise[b] (Diffusion.py:281-284; contraction is off: two
+// products and one sum in fp32). noise null: the Philox stream of (seed, sample_base + b, round).
+__global__ __launch_bounds__(SNT) void q_sample_kernel(float* xt, const float* x0, const float* noise, float* noise_out,
+                                                       int n, const float2* qc, uint64_t seed, int sample_base,
+                                                       int round) {
+  const int b = blockIdx.y;
+  const float2 c = qc[b];
+  const float* xb = x0 + (long)b * n;
+  const float* nb = noise ? noise + (long)b * n : nullptr;
+  float* ob = xt + (long)b * n;
+  float* zb = noise_out ? noise_out + (long)b * n : nullptr;
+  const int e0 = blockIdx.x * SCH, e1 = min(n, e0 + SCH);
+  const bool vec = vec4_ok(n, xt, x0, noise, noise_out);
+  for (int e = e0 + 4 * threadIdx.x; e < e1; e += 4 * SNT) {
+    float xv[4], z[4], o[4];
+    load4(xb, e, e1, vec, xv);
+    if (nb) load4(nb, e, e1, vec, z);
+    else philox_normal4(seed, sample_base + b, round, Q_SAMPLE_STREAM, e, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) o[j] = c.x * xv[j] + c.y * z[j];
+    store4(ob, e, e1, vec, o);
+    if (zb) store4(zb, e, e1, vec, z);
+  }
+}
+
+// pred_x0 and the loss partials of one chunk (Diffusion.py:294-319). CLIP: the threshold comes from
+// the four per-sample-coefficient count launches before this one, as in sampler_final_kernel<true>.
+// loss_type 0: sum |noise - eps|; 1: sum (10 noise - 10 eps)^2 — fp32 terms, summed in fp64 per
+// thread, then over the workgroup in a fixed order, stored to part[b][chunk].
+template <bool CLIP>
+__global__ __launch_bounds__(SNT) void x0_loss_kernel(const float* xt, const float* eps, const float* noise, int n,
+                                                      const StepCoef* coefs, int loss_type, int k_lo, int k_hi,
+                                                      float q_w, float* pred_x0, double* part, float* thresh_out,
+                                                      unsigned* ws) {
+  __shared__ float vs[2];
+  __shared__ double red[SNT];
+  const SelLayout L{(int)gridDim.y, (int)gridDim.x};
+  const int b = blockIdx.y;
+  const StepCoef c = coefs[b];
+  float s = 1.f;
+  if (CLIP) {
+    const int nsel = k_hi == k_lo ? 1 : 2;
+    if (threadIdx.x < 64 * nsel) {
+      const int sl = threadIdx.x >> 6;
+      unsigned pf, mk, rk;
+      sel_state<4>(ws, L, b, sl, (unsigned)(sl ? k_hi : k_lo), false, pf, mk, rk);
+      if ((threadIdx.x & 63) == 0) vs[sl] = __uint_as_float(pf);
+    }
+    __syncthreads();
+    const float vlo = vs[0], vhi = nsel > 1 ? vs[1] : vs[0];
+    // torch lerp (CPU): w < 0.5 ? a + w (b - a) : b - (b - a)(1 - w)
+    s = q_w < 0.5f ? vlo + q_w * (vhi - vlo) : vhi - (vhi - vlo) * (1.f - q_w);
+    if (s < 1.f) s = 1.f;
+    if (thresh_out && blockIdx.x == 0 && threadIdx.x == 0) thresh_out[b] = s;
+  }
+  const float* xb = xt + (long)b * n;
+  const float* eb = eps + (long)b * n;
+  const float* nb = noise + (long)b * n;
+  float* pb = pred_x0 + (long)b * n;
+  const int e0 = blockIdx.x * SCH, e1 = min(n, e0 + SCH);
+  const bool vec = vec4_ok(n, xt, eps, noise, pred_x0);
+  double acc = 0.0;
+  for (int e = e0 + 4 * threadIdx.x; e < e1; e += 4 * SNT) {
+    float xv[4], ev[4], z[4], o[4];
+    load4(xb, e, e1, vec, xv);
+    load4(eb, e, e1, vec, ev);
+    load4(nb, e, e1, vec, z);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float x0 = c.sra * xv[j] - c.srm1 * ev[j];
+      o[j] = CLIP ? fminf(fmaxf(x0, -s), s) / s : x0;
+      float term;
+      if (loss_type == 0) {
+        term = fabsf(z[j] - ev[j]);
+      } else {
+        const float d = z[j] * 10.f - ev[j] * 10.f;
+        term = d * d;
+      }
+      if (e + j < e1) acc += (double)term;
+    }
+    store4(pb, e, e1, vec, o);
+  }
+  const double tot = block_sum_fixed(acc, red);
+  if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = tot;
+}
+
+// sum |a - b| of one chunk of sample b, as above (the rec losses' L1 numerator)
+__global__ __launch_bounds__(SNT) void abs_diff_kernel(const float* a, const float* b2, int n, double* part) {
+  __shared__ double red[SNT];
+  const int b = blockIdx.y;
+  const float* ab = a + (long)b * n;
+  const float* bb = b2 + (long)b * n;
+  const int e0 = blockIdx.x * SCH, e1 = min(n, e0 + SCH);
+  const bool vec = vec4_ok(n, a, b2, nullptr, nullptr);
+  double acc = 0.0;
+  for (int e = e0 + 4 * threadIdx.x; e < e1; e += 4 * SNT) {
+    float av[4], bv[4];
+    load4(ab, e, e1, vec, av);
+    load4(bb, e, e1, vec, bv);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (e + j < e1) acc += (double)fabsf(av[j] - bv[j]);
+  }
+  const double tot = block_sum_fixed(acc, red);
+  if (threadIdx.x == 0) part[(size_t)b * gridDim.x + blockIdx.x] = tot;
+}
+
+// sums[b] = part[b][0] + part[b][1] + ... in chunk order (one thread per sample)
+__global__ void chunk_sum_kernel(const double* part, int B, int nch, double* sums) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  double t = 0.0;
+  for (int k = 0; k < nch; ++k) t += part[(size_t)b * nch + k];
+  sums[b] = t;
 }
 
 // t and the step counter for the next step (one workgroup, after the update launch: every
@@ -439,13 +599,56 @@ void sampler_step_mw(hipStream_t s, float* x, const float* eps, int B, int n, co
                      const float* noise, uint64_t seed, int sample_base, int round, int k_lo, int k_hi, float q_w,
                      float* thresh_out, unsigned* ws, int* t_next, int nsteps) {
   const dim3 grid((n + SCH - 1) / SCH, B);
-  hipLaunchKernelGGL(radix_count_kernel<0>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(radix_count_kernel<1>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(radix_count_kernel<2>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(radix_count_kernel<3>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(sampler_final_kernel, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, noise, B, seed,
+  hipLaunchKernelGGL((radix_count_kernel<0, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<1, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<2, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<3, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL(sampler_final_kernel<false>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, noise, B, seed,
                      sample_base, round, k_lo, k_hi, q_w, thresh_out, ws);
   if (t_next) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(256), 0, s, step_ctr, coefs, t_next, B, nsteps);
+}
+
+void sampler_step_t(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs, const float* noise,
+                    int k_lo, int k_hi, float q_w, float* thresh_out, unsigned* ws) {
+  const dim3 grid((n + SCH - 1) / SCH, B);
+  hipLaunchKernelGGL((radix_count_kernel<0, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<1, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<2, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<3, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL(sampler_final_kernel<true>, grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, noise, B,
+                     (uint64_t)0, 0, 0, k_lo, k_hi, q_w, thresh_out, ws);
+}
+
+void q_sample(hipStream_t s, float* xt, const float* x0, const float* noise, float* noise_out, int B, int n,
+              const float2* qc, uint64_t seed, int sample_base, int round) {
+  hipLaunchKernelGGL(q_sample_kernel, dim3((n + SCH - 1) / SCH, B), dim3(SNT), 0, s, xt, x0, noise, noise_out, n, qc,
+                     seed, sample_base, round);
+}
+
+int loss_chunks(int n) { return (n + SCH - 1) / SCH; }
+
+void x0_loss(hipStream_t s, const float* xt, const float* eps, const float* noise, int B, int n, const StepCoef* coefs,
+             int loss_type, bool clip, int k_lo, int k_hi, float q_w, float* pred_x0, double* part, double* loss_sum,
+             float* thresh_out, unsigned* ws) {
+  const dim3 grid((n + SCH - 1) / SCH, B);
+  if (clip) {
+    hipLaunchKernelGGL((radix_count_kernel<0, true>), grid, dim3(SNT), 0, s, xt, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+    hipLaunchKernelGGL((radix_count_kernel<1, true>), grid, dim3(SNT), 0, s, xt, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+    hipLaunchKernelGGL((radix_count_kernel<2, true>), grid, dim3(SNT), 0, s, xt, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+    hipLaunchKernelGGL((radix_count_kernel<3, true>), grid, dim3(SNT), 0, s, xt, eps, n, coefs, nullptr, ws, k_lo, k_hi);
+    hipLaunchKernelGGL(x0_loss_kernel<true>, grid, dim3(SNT), 0, s, xt, eps, noise, n, coefs, loss_type, k_lo, k_hi, q_w,
+                       pred_x0, part, thresh_out, ws);
+  } else {
+    hipLaunchKernelGGL(x0_loss_kernel<false>, grid, dim3(SNT), 0, s, xt, eps, noise, n, coefs, loss_type, k_lo, k_hi,
+                       q_w, pred_x0, part, thresh_out, ws);
+  }
+  hipLaunchKernelGGL(chunk_sum_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, B, (int)grid.x, loss_sum);
+}
+
+void abs_diff_sum(hipStream_t s, const float* a, const float* b, int B, int n, double* part, double* sums) {
+  const dim3 grid((n + SCH - 1) / SCH, B);
+  hipLaunchKernelGGL(abs_diff_kernel, grid, dim3(SNT), 0, s, a, b, n, part);
+  hipLaunchKernelGGL(chunk_sum_kernel, dim3((B + 63) / 64), dim3(64), 0, s, part, B, (int)grid.x, sums);
 }
 
 void fill_normal(hipStream_t s, float* x, int B, int n, uint64_t seed, int sample_base, int round, int stream_id) {

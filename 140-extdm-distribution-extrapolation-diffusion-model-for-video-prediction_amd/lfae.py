@@ -211,7 +211,8 @@ class Generator(_NativeModule):
 
 
 class FlowDiffusion(nn.Module):
-    """FlowDiffusion (VideoFlowDiffusion_multi_w_ref.py:18-118), sampling half.
+    """FlowDiffusion (VideoFlowDiffusion_multi_w_ref.py:18-316): sample_one_video and, with
+    is_train=True, forward's teacher-forced evaluation step (no gradients).
 
     `wrapper` picks the reference wrapper whose sample_one_video is mirrored:
     'multi_w_ref' (default; u12/u22/ada, channels 256+256, init_noise_conv path),
@@ -224,8 +225,9 @@ class FlowDiffusion(nn.Module):
                  withFea=True, Unet3D_architecture="DenoiseNet_STWAtt_w_w_ref_adaptor_cross_multi_traj_ada",
                  wrapper='multi_w_ref'):
         super().__init__()
-        if is_train:
-            raise NotImplementedError('training (FlowDiffusion.forward / p_losses) is out of scope')
+        # is_train=True enables forward's teacher-forced evaluation step (the reference's validation
+        # step) under no_grad; gradients, optimiser and training loop stay out of scope
+        self.is_train = bool(is_train)
         fp = config['flow_params']['model_params']
         dp = config['diffusion_params']['model_params']
         ds = config['dataset_params']
@@ -276,23 +278,26 @@ class FlowDiffusion(nn.Module):
         self.frame_num = tc + tp
 
     @torch.no_grad()
-    def encode(self, real_vid):
+    def encode(self, real_vid, nf=None):
         """The encoder part of sample_one_video (multi_w_ref.py:223-275 /
-        multi1248.py:213-257): per cond frame, region and background params vs
+        multi1248.py:213-257): per frame, region and background params vs
         the reference frame (cond frame tc-1), Generator.forward; the conditioning
-        x_cond and cond_fea. All tc frames go through each module in one batched call."""
+        x_cond and cond_fea. All nf frames (default: the tc cond frames; forward: all tc + tp)
+        go through each module in one batched call; the real_* entries and x_cond then hold nf
+        frames, cond_fea is the same for any nf."""
         tc, tp = self.cond_frame_num, self.pred_frame_num
+        nf = tc if nf is None else nf
         B = real_vid.shape[0]
         vid = real_vid.float()
         ref = vid[:, :, tc - 1].contiguous()
-        frames = vid.permute(2, 0, 1, 3, 4).reshape(tc * B, *vid.shape[1:2], *vid.shape[3:]).contiguous()
-        refs = ref.repeat(tc, 1, 1, 1)
+        frames = vid[:, :, :nf].permute(2, 0, 1, 3, 4).reshape(nf * B, *vid.shape[1:2], *vid.shape[3:]).contiguous()
+        refs = ref.repeat(nf, 1, 1, 1)
         src_p = self.region_predictor(ref)
-        src_p = {k: v.repeat(tc, *([1] * (v.dim() - 1))) for k, v in src_p.items()}
+        src_p = {k: v.repeat(nf, *([1] * (v.dim() - 1))) for k, v in src_p.items()}
         drv_p = self.region_predictor(frames)
         bg = self.bg_predictor(refs, frames)
         g = self.generator(refs, source_region_params=src_p, driving_region_params=drv_p, bg_params=bg)
-        tb = lambda x: x.reshape(tc, B, *x.shape[1:]).movedim(0, 2)  # (tc*B, ...) -> (B, ..., tc, ...)
+        tb = lambda x: x.reshape(nf, B, *x.shape[1:]).movedim(0, 2)  # (nf*B, ...) -> (B, ..., nf, ...)
         ret = {'real_vid_grid': tb(g['optical_flow'].permute(0, 3, 1, 2)).contiguous()}
         if self.estimate_occlusion_map:
             ret['real_vid_conf'] = tb(g['occlusion_map']).contiguous()
@@ -300,7 +305,7 @@ class FlowDiffusion(nn.Module):
         ret['real_warped_vid'] = tb(g['deformed']).contiguous()
         # cond_fea: forward_bottle of cond frames 0..tc-2, then the last generator call's
         # bottle_neck_feat (the bottleneck of the reference frame) repeated
-        ref_fea = g['bottle_neck_feat'][(tc - 1) * B:]
+        ref_fea = g['bottle_neck_feat'][(tc - 1) * B:tc * B]
         early = self.generator.forward_bottle(frames[:(tc - 1) * B]) if tc > 1 else ref_fea[:0]
         early = early.reshape(tc - 1, B, *ref_fea.shape[1:])
         if self.wrapper == 'multi1248':
@@ -341,6 +346,43 @@ class FlowDiffusion(nn.Module):
             ret['sample_vid_conf'] = conf
         ret['sample_out_vid'] = out
         ret['sample_warped_vid'] = warped
+        return ret
+
+    @torch.no_grad()
+    def forward(self, real_vid, t=None, noise=None, seed=None):
+        """The reference wrapper's forward (multi_w_ref.py:118-221, multi_w_ref_u22.py:239-413,
+        multi1248.py:108-211) under no_grad: the pseudo ground-truth flow of all tc + tp frames, one
+        teacher-forced diffusion step on the future frames' flow (GaussianDiffusion.forward), and
+        the decode of the thresholded x0. is_train=False returns the real_* keys only. t / noise
+        are injected for parity runs; otherwise t is drawn by torch.randint on the device and the
+        noise by the native Philox stream (seed)."""
+        _need_device(real_vid)
+        tc, tp = self.cond_frame_num, self.pred_frame_num
+        if not self.estimate_occlusion_map:
+            raise KeyError('occlusion_map')  # forward reads generated["occlusion_map"] unconditionally
+        ret, frames, fea, ref = self.encode(real_vid, nf=tc + tp)
+        if not self.is_train:
+            return ret
+        B = frames.shape[0]
+        self.diffusion.max_batch = max(self.diffusion.max_batch, B)
+        kw = {} if seed is None else {'seed': seed}
+        loss, pred = self.diffusion(frames[:, :, :tc].contiguous(), frames[:, :, tc:tc + tp].contiguous(), fea, t=t,
+                                    noise=noise, **kw)
+        ret['loss'] = loss
+        grid = pred[:, :2].contiguous()
+        conf = ((pred[:, 2].unsqueeze(1) + 1) * 0.5).contiguous()
+        out, warped = self.generator.decode_frames(ref, grid, conf, with_warped=True)
+        target = real_vid.float()[:, :, tc:tc + tp].contiguous()
+        # nn.L1Loss of the frames; multi_w_ref_u22 scales both operands by 10 (:397-398)
+        k = 10 if self.wrapper == 'multi_w_ref_u22' else 1
+        tk = target * k if k != 1 else target
+        for name, fake in (('rec_loss', out), ('rec_warp_loss', warped)):
+            sums = _lib.abs_diff_sum(tk, fake * k if k != 1 else fake)
+            ret[name] = (sums.sum() / target.numel()).to(torch.float32)
+        ret['fake_vid_grid'] = grid
+        ret['fake_vid_conf'] = conf
+        ret['fake_out_vid'] = out
+        ret['fake_warped_vid'] = warped
         return ret
 
     def sample_one_video(self, cond_scale, real_vid, **sample_kw):

@@ -5,7 +5,7 @@
   Unet3DAdaU22       DenoiseNet_STWAtt_w_w_ref_adaptor_cross_multi_traj_ada_u22.py:1009-1306
   Unet3DWoRef        DenoiseNet_STWAtt_w_wo_ref_adaptor_cross_multi.py:755-967
   UNET3D_BY_MODULE   reference module name -> class (what FlowDiffusion imports)
-  GaussianDiffusion  model/BaseDM_adaptor/Diffusion.py:52-258
+  GaussianDiffusion  model/BaseDM_adaptor/Diffusion.py:52-327 (no gradients)
   Generator          model/LFAE/generator.py (decoder: forward_with_flow)
 
 Constructor signatures, method names, argument meaning, assertions and the
@@ -247,8 +247,9 @@ def ddim_time_pairs(total_timesteps, sampling_timesteps):
 
 
 class GaussianDiffusion(nn.Module):
-    """GaussianDiffusion (Diffusion.py:52-258), sampling half. The reverse loop
-    runs natively: one captured hipGraph step replayed S times."""
+    """GaussianDiffusion (Diffusion.py:52-327): the sampling half (the reverse loop runs natively,
+    one captured hipGraph step replayed S times) and the teacher-forced evaluation step
+    (q_sample / p_losses / forward, inference only)."""
 
     def __init__(self, denoise_fn, *, image_size, num_frames, text_use_bert_cls=False, channels=3, timesteps=1000,
                  sampling_timesteps=250, ddim_sampling_eta=1., loss_type='l1', use_dynamic_thres=True,
@@ -324,11 +325,62 @@ class GaussianDiffusion(nn.Module):
         if noise is None:
             noise = torch.randn_like(x)
         out = x.clone().contiguous()
-        tt = int(t[0].item())
-        assert bool((t == tt).all()), 'the native step takes one t for the whole batch'
         h = self._native(x.shape[0], x.device, cond_fea.shape[-1])
-        h.sampler_step(_lib.SAMPLER_DDPM, tt, 0, 0., out, eps.contiguous(), noise.contiguous()[None])
+        if bool((t == t[0]).all()):
+            h.sampler_step(_lib.SAMPLER_DDPM, int(t[0].item()), 0, 0., out, eps.contiguous(), noise.contiguous()[None])
+        else:
+            # a mixed t: the same update with per-sample coefficients (extdm_sampler_step_t)
+            tt = t.to(device=x.device, dtype=torch.int64).contiguous()
+            h.sampler_step_t(_lib.SAMPLER_DDPM, tt, None, 0., out, eps.contiguous(), noise.contiguous())
         return out
+
+    # -- teacher-forced evaluation step (Diffusion.py:276-327), inference only ----
+    def _t(self, t, x):
+        return t.to(device=x.device, dtype=torch.int64).contiguous()
+
+    @torch.no_grad()
+    def q_sample(self, x_start, t, noise=None, seed=None, sample_base=0, round_idx=0):
+        """Diffusion.py:276-284. noise None: the native Philox stream keyed by (seed, global sample
+        index, round); seed None draws one from torch's default generator."""
+        if not x_start.is_cuda:
+            raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
+        x0 = x_start.float().contiguous()
+        out = torch.empty_like(x0)
+        seed = (self._seed() if seed is None else seed) if noise is None else 0
+        h = self._native(x0.shape[0], x0.device)
+        h.q_sample(self._t(t, x0), x0, out, noise=None if noise is None else noise.float().contiguous(), seed=seed,
+                   sample_base=sample_base, round_idx=round_idx)
+        return out
+
+    @torch.no_grad()
+    def p_losses(self, x_start_cond, x_start_pred, cond_fea, t, cond=None, noise=None, clip_denoised=True, seed=None,
+                 sample_base=0, round_idx=0, return_sums=False):
+        """Diffusion.py:286-319 under no_grad: noise x_start_pred to t, run the denoiser once, return
+        (loss, pred_x0) with loss a 0-dim fp32 tensor = loss_sum.sum() / (B n), loss_sum the per-sample
+        fp64 sums of the native reduction (also returned with return_sums=True). The denoiser has no
+        conditioning to drop, so null_cond_prob has no effect (as in the reference's has_cond=False)."""
+        if self.loss_type not in _lib.LOSS_TYPES:
+            raise NotImplementedError()
+        if not x_start_pred.is_cuda:
+            raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
+        x0 = x_start_pred.float().contiguous()
+        B = x0.shape[0]
+        pred_x0 = torch.empty_like(x0)
+        loss_sum = torch.empty(B, device=x0.device, dtype=torch.float64)
+        seed = (self._seed() if seed is None else seed) if noise is None else 0
+        nz = None if noise is None else noise.float().contiguous()
+        tt = self._t(t, x0)
+        self._run_sampler(B, x0.device, cond_fea.shape[-1], lambda h: h.p_losses(
+            tt, x_start_cond.float().contiguous(), x0, cond_fea.float().contiguous(), self.loss_type, clip_denoised,
+            pred_x0, loss_sum, noise=nz, seed=seed, sample_base=sample_base, round_idx=round_idx))
+        loss = (loss_sum.sum() / x0.numel()).to(torch.float32)
+        return (loss, pred_x0, loss_sum) if return_sums else (loss, pred_x0)
+
+    def forward(self, x_cond, x_pred, cond_fea, t=None, noise=None, **kwargs):
+        """Diffusion.py:321-327; t defaults to torch.randint on the device like the reference."""
+        if t is None:
+            t = torch.randint(0, self.num_timesteps, (x_cond.shape[0],), device=x_cond.device).long()
+        return self.p_losses(x_cond, x_pred, cond_fea, t, cond=None, noise=noise, **kwargs)
 
     @torch.inference_mode()
     def p_sample_loop(self, x_cond, shape, cond_fea, cond=None, cond_scale=1., x_T=None, noise=None, seed=None,

@@ -22,6 +22,13 @@
  *                                                   Diffusion.py:180-189, 209-258
  *   extdm_sampler_step   one p_sample / DDIM update given eps
  *                                                   Diffusion.py:145-177, 231-255
+ *   extdm_sampler_step_t the same update with a per-sample t (p_sample with a mixed t)
+ *   extdm_q_sample       GaussianDiffusion.q_sample                 Diffusion.py:276-284
+ *   extdm_x0_loss        p_losses after the denoiser (loss, thresholded x0)
+ *                                                   Diffusion.py:294-319
+ *   extdm_p_losses       GaussianDiffusion.p_losses / forward       Diffusion.py:286-327
+ *   extdm_abs_diff_sum   nn.L1Loss()(pred_frames, fake_out_vid) (rec_loss, rec_warp_loss)
+ *                                                   VideoFlowDiffusion_multi_w_ref.py:212-213
  *   extdm_decode         Generator.forward_with_flow   LFAE/generator.py:152-206
  *   extdm_region_params  RegionPredictor.forward       LFAE/region_predictor.py:62-150
  *   extdm_bg_params      BGMotionPredictor.forward     LFAE/bg_motion_predictor.py:47-64
@@ -128,6 +135,49 @@ int extdm_record_thresholds(ExtdmHandle* h, float* buf, int64_t cap);
 /* One sampler update in place on x given eps (the step-k coefficients). */
 int extdm_sampler_step(ExtdmHandle* h, int B, int sampler, int t, int t_next, float eta, float* x, const float* eps,
                        const float* noise, float* thresh_out, void* stream);
+
+/* ---- Teacher-forced evaluation step (Diffusion.py:276-327), inference only --------------
+ * Every t (and t_next) is a device int64 [B] vector as in extdm_unet_forward, each in
+ * [0, timesteps); the calls read it back to build the per-sample coefficient table on the host
+ * in fp32 with the reference's expressions (they synchronise `stream`). A sample's results never
+ * depend on the batch it sits in or on the other samples' t. */
+
+/* One sampler update in place on x given eps, sample b at its own t[b] (DDIM: towards
+ * t_next[b]; DDPM ignores t_next, which may be NULL). noise: [B][n] (or NULL when no sample
+ * uses noise), thresh_out: [B] or NULL. Sample b's result equals extdm_sampler_step at t[b]
+ * bit for bit. */
+int extdm_sampler_step_t(ExtdmHandle* h, int B, int sampler, const int64_t* t, const int64_t* t_next, float eta,
+                         float* x, const float* eps, const float* noise, float* thresh_out, void* stream);
+
+/* x_t[b] = sqrt_alphas_cumprod[t_b] x0[b] + sqrt_one_minus_alphas_cumprod[t_b] noise[b] in fp32
+ * in that order. noise NULL: the sampler's Philox stream keyed by (seed, sample_base + b, round)
+ * under a stream id no x_T or step uses; the drawn noise goes to noise_out when non-NULL. */
+int extdm_q_sample(ExtdmHandle* h, int B, const int64_t* t, const float* x0, const float* noise, uint64_t seed,
+                   int sample_base, int round, float* noise_out, float* x_t, void* stream);
+
+/* The part of p_losses after the denoiser: pred_x0 = x0_hat = sqrt_recip[t] x_t - sqrt_recipm1[t] eps,
+ * with clip_denoised != 0 clamped to +-s and divided by s = max(1, quantile(|x0_hat|, 0.9)) (exact
+ * order statistics; s to thresh_out[B] when non-NULL), else raw. loss_sum[b] (device double [B]) =
+ * sum |noise - eps| (L1) or sum (10 noise - 10 eps)^2 (L2) over sample b: fp32 terms added in
+ * fp64 in a fixed order. The reference's mean loss is sum_b loss_sum[b] / (B n). */
+enum { EXTDM_LOSS_L1 = 0, EXTDM_LOSS_L2 = 1 };
+int extdm_x0_loss(ExtdmHandle* h, int B, const int64_t* t, const float* x_t, const float* eps, const float* noise,
+                  int loss_type, int clip_denoised, float* pred_x0, double* loss_sum, float* thresh_out,
+                  void* stream);
+
+/* q_sample, the denoiser forward and x0_loss chained on the handle's workspace. x_cond: [B,3,tc,L,L],
+ * x_start / pred_x0: [B,3,tp,L,L], cond_fea as in extdm_unet_forward, noise as in extdm_q_sample.
+ * Fails like extdm_sample when the F16X3 range flag is raised by the forward. */
+int extdm_p_losses(ExtdmHandle* h, int B, const int64_t* t, const float* x_cond, const float* x_start,
+                   const float* cond_fea, const float* noise, uint64_t seed, int sample_base, int round, int loss_type,
+                   int clip_denoised, float* pred_x0, double* loss_sum, void* stream);
+
+/* sums[b] = sum_i |a[b][i] - b[b][i]|, i < n, in fp64 in a fixed order (the numerator of the
+ * reference wrappers' rec_loss / rec_warp_loss, nn.L1Loss). a, b: contiguous device fp32 [B][n];
+ * sums: device double [B]; work: device scratch of B x extdm_abs_diff_chunks(n) doubles. Not tied
+ * to a handle. */
+int extdm_abs_diff_chunks(int n);
+int extdm_abs_diff_sum(const float* a, const float* b, int B, int n, double* sums, double* work, void* stream);
 
 /* Measurement hook for bench.py: time `iters` launches of one hot-path conv
  * exactly as the forward issues it, on random operands, with HIP events on the
