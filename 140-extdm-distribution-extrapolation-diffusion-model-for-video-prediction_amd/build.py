@@ -46,7 +46,8 @@ OPT = {}
 def _needs(obj, src):
     if not os.path.exists(obj):
         return True
-    deps = [src, os.path.join(os.path.dirname(src), 'kernels.h'), os.path.join(os.path.dirname(src), 'attn_x3_ops.h'), os.path.join(INCLUDE, 'extdm.h'), os.path.abspath(__file__)]
+    d = os.path.dirname(src)
+    deps = [src, os.path.join(INCLUDE, 'extdm.h'), os.path.abspath(__file__)] + [os.path.join(d, h) for h in os.listdir(d) if h.endswith('.h')]
     return any(os.path.getmtime(d) > os.path.getmtime(obj) for d in deps)
 
 

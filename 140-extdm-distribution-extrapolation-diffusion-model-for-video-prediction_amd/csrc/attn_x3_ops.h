@@ -1,7 +1,10 @@
-// Shared device helpers of the fused f16x3 attention kernels (stw_x3.hip, stw64_x3.hip):
-// the MFMA fragment types, the compiler-visible hi / lo split, the f16x3 product, the
-// half-wave reductions and the attention operand of one k-step in either arithmetic
-// (f16x3 hi / lo, or bf16 for EXTDM_PRECISION_BF16_ATTN).
+// Shared pieces of the fused f16x3 attention kernels (stw_x3.hip, and through attn64_core.h
+// stw64_x3.hip and temporal64_x3.hip): the packed unit layout of their weights, the MFMA
+// fragment types, the compiler-visible hi / lo split, the f16x3 product, the packed exp2 of the
+// softmax, the half-wave reductions and the attention operand of one k-step in either
+// arithmetic (f16x3 hi / lo, or bf16 for EXTDM_PRECISION_BF16_ATTN). The 64-token kernels'
+// common core (weight loader, operand scaling, unit loop, launch helpers) builds on these in
+// attn64_core.h.
 #pragma once
 #include "kernels.h"
 
@@ -11,6 +14,17 @@ namespace attn_ops {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
+
+// Packed unit slice (halves) of packed_attn_x3 (runtime.cpp, attn_x3_unit_halves): [q: C/16 frags]
+// [k: C/16][v: C/16][proj: C/32 tiles x 2 k-steps], each frag = [hi|lo][64 lanes][8].
+template <int C>
+struct UnitLayout {
+  static constexpr int KS = C / 16;
+  static constexpr int FRAG = 2 * 512;  // halves per frag (hi + lo)
+  static constexpr int Q = 0, K = KS * FRAG, V = 2 * KS * FRAG, P = 3 * KS * FRAG;
+  static constexpr int HALVES = 3 * KS * FRAG + (C / 32) * 2 * FRAG;
+};
+
 // s <- exp2(s c - m) over NT accumulator tiles, returning the lane's sum: the exponent argument and
 // the running sum as packed pairs (16 v_pk_fma + 16 v_pk_add per 32 values instead of 64 VALU)
 template <int NT>

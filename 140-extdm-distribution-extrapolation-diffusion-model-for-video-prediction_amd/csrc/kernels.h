@@ -354,7 +354,8 @@ bool temporal_x3(hipStream_t s, const View& x, const View& out, const AttnGeom& 
                  const float* mbias, const float* rcos, const float* rsin, float q_scale, bool bf16);
 // The same layer for clips of 33..64 frames (temporal64_x3.hip): two waves per pixel, 64 frame
 // slots, C in {64, 128}, dim_head 16 or 32; the stw_x3 weight packing; mbias [8][64][64] (T5 bias,
-// -inf for key frames >= D, times 2^(e_q + e_k)); out shares x's strides and may alias x.
+// -inf for key frames >= D, times 2^(e_q + e_k)); out shares x's strides and may alias x; bf16 at
+// dim_head 32 only (false at 16: temporal_long() routes that elsewhere).
 bool temporal64_x3_supported(int C, int frames, int dim_head, int heads);
 bool temporal64_x3(hipStream_t s, const View& x, const View& out, const AttnGeom& g, int heads, int dim_head,
                    const float* gamma, const float* ln_w, const float* ln_b, const void* wpk, const float* wsc,

@@ -81,16 +81,6 @@ __device__ __forceinline__ Tok token_of(int tk, const AttnGeom& g, long st, int 
   return o;
 }
 
-// Packed unit slice (halves): [q: C/16 frags][k: C/16][v: C/16][proj: C/32 tiles x 2 k-steps],
-// each frag = [hl][64 lanes][8].
-template <int C>
-struct UnitLayout {
-  static constexpr int KS = C / 16;
-  static constexpr int FRAG = 2 * 512;  // halves per frag (hi + lo)
-  static constexpr int Q = 0, K = KS * FRAG, V = 2 * KS * FRAG, P = 3 * KS * FRAG;
-  static constexpr int HALVES = 3 * KS * FRAG + (C / 32) * 2 * FRAG;
-};
-
 // mbias: [npat][8 heads][32 queries][32 keys] fp32, the relative-position bias with the
 // masks folded in (build_mask_bias, runtime.cpp): -100 for a shifted window's region
 // mismatch (u12:414-436), -inf for keys past the window's N tokens and for another

@@ -35,27 +35,22 @@
 // again the same way (an L2 hit), adds Y + the residual in place (each (channel, frame, pixel) is
 // one lane's) and the tile leaves as the same 16-B pieces. C = 128 (4 waves, two pixels per
 // workgroup, ring + exchange fill the LDS) and unaligned geometries take the per-lane path.
-#include <algorithm>
+//
+// The unit loop below is still this file's own copy of attn64_core.h's unit_loop (and of its
+// load_unit / scale_split): calling the shared functions compiled to 19 more instructions per wave
+// outside the loop (64-bit vector addresses for unit 0's weight DMA, two SGPR spills, unpaired
+// zeroing moves) and measured 0.28 % slower on the 50-frame KTH layer, past the parent's 0.24 %
+// spread (profiles/attn64_core_refactor.json). A fix to the core goes into both places. The
+// layout, the XCD slot and the launch pieces are the shared ones.
 #include <cstdlib>
-#include <mutex>
 
-#include "attn_x3_ops.h"
+#include "attn64_core.h"
 
 namespace extdm {
 
 namespace {
 
 using namespace attn_ops;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// Packed unit slice (halves) — the stw_x3.hip layout (attn_x3_unit_halves)
-template <int C>
-struct ULT {
-  static constexpr int KS = C / 16;
-  static constexpr int FRAG = 2 * 512;
-  static constexpr int Q = 0, K = KS * FRAG, V = 2 * KS * FRAG, P = 3 * KS * FRAG;
-  static constexpr int HALVES = 3 * KS * FRAG + (C / 32) * 2 * FRAG;
-};
 
 template <int C, int DH, int NW, bool BF, bool TILE>
 __global__ __launch_bounds__(NW * 64) void temporal64_x3_kernel(const float* x, float* out, long sb, long sc, long st,
@@ -69,7 +64,7 @@ __global__ __launch_bounds__(NW * 64) void temporal64_x3_kernel(const float* x, 
                                                                 const float* __restrict__ rsin, float q_scale,
                                                                 int total_groups, int* __restrict__ range_flag,
                                                                 int remap) {
-  using UL = ULT<C>;
+  using UL = UnitLayout<C>;
   constexpr int KS = UL::KS;
   constexpr int UNITS = 8 * DH / 32;  // heads 8
   constexpr int HPU = 32 / DH;
@@ -87,10 +82,8 @@ __global__ __launch_bounds__(NW * 64) void temporal64_x3_kernel(const float* x, 
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int tt = wave & 1;
   const int h = lane >> 5, lc = lane & 31;
-  // XCD-contiguous workgroup order (grid a multiple of 8, host): consecutive logical workgroups,
-  // whose pixels share 128-B lines, run on one XCD
-  const int G8 = (int)gridDim.x;
-  const int bid = remap ? (int)((blockIdx.x & 7) * (G8 >> 3) + (blockIdx.x >> 3)) : (int)blockIdx.x;
+  // XCD-contiguous order: consecutive logical workgroups, whose pixels share 128-B lines, on one XCD
+  const int bid = xcd_slot(remap);
   const int gidx = bid * WPG + (wave >> 1);  // the wave's pixel
   const bool active = gidx < total_groups;
   // TILE: HW is a multiple of WPG (host), so a workgroup is wholly inside one sample or inactive
@@ -456,31 +449,16 @@ template <int C, int DH, int NW, bool BF>
 void launch(hipStream_t s, const View& x, const View& out, const AttnGeom& g, const float* gamma, const float* ln_w,
             const float* ln_b, const void* wpk, const float* wsc, const float* mbias, const float* rcos,
             const float* rsin, float q_scale) {
-  constexpr int XS = 2 * 2 * Op<BF>::SLOTS;
   constexpr bool TILE_OK = C == 64 && NW == 8;
   const int HW = g.H * g.W;
   const bool tile = TILE_OK && t64_tile_ok(x, out, HW);
-  const size_t ring = (size_t)2 * ULT<C>::HALVES * sizeof(_Float16);
-  const size_t xch = (size_t)NW * XS * 64 * 16;
-  const size_t tileb = (size_t)C * 256 * sizeof(float);
-  const size_t lds = ring + (tile ? std::max(xch, tileb) : xch);
-  static std::once_flag once[64];
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  std::call_once(once[dev & 63], [] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal64_x3_kernel<C, DH, NW, BF, false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (TILE_OK)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&temporal64_x3_kernel<C, DH, NW, BF, TILE_OK>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  });
+  const size_t lds = attn64_lds<C, NW, BF>(tile ? (size_t)C * 256 * sizeof(float) : 0);
+  allow_full_lds<&temporal64_x3_kernel<C, DH, NW, BF, false>, &temporal64_x3_kernel<C, DH, NW, BF, TILE_OK>>();
   const int total = x.B * HW;
-  // EXTDM_T64_XCD=0: dispatch order (A/B); else the grid rounded up to a multiple of 8 for the
-  // XCD-contiguous order (the extra workgroups' pixels lie past `total`: inactive)
+  // EXTDM_T64_XCD=0: dispatch order (A/B)
   static const bool xcd = [] { const char* v = getenv("EXTDM_T64_XCD"); return !(v && v[0] == '0'); }();
-  int grid = (total + NW / 2 - 1) / (NW / 2);
-  const int remap = xcd && grid >= 64 ? 1 : 0;
-  if (remap) grid = (grid + 7) & ~7;
+  int remap;
+  const int grid = xcd_grid(total, NW, xcd, remap);
   note_kernel("temporal64_x3_kernel<%d, %d, %d, %s, %s>", C, DH, NW, BF ? "true" : "false", tile ? "true" : "false");
   auto kern = tile ? &temporal64_x3_kernel<C, DH, NW, BF, TILE_OK> : &temporal64_x3_kernel<C, DH, NW, BF, false>;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, s, x.p, out.p, x.sb, x.sc, x.st, g.D, HW, gamma, ln_w, ln_b,
@@ -504,7 +482,7 @@ bool dispatch(hipStream_t s, const View& x, const View& out, const AttnGeom& g, 
 
 bool temporal64_x3_supported(int C, int frames, int dim_head, int heads) {
   return heads == 8 && (C == 64 || C == 128) && frames > 32 && frames <= 64 && (dim_head == 32 || dim_head == 16) &&
-         attn_x3_unit_halves(C) == (C == 64 ? ULT<64>::HALVES : ULT<128>::HALVES);
+         attn_x3_unit_halves(C) == (C == 64 ? UnitLayout<64>::HALVES : UnitLayout<128>::HALVES);
 }
 
 bool temporal64_x3(hipStream_t s, const View& x, const View& out, const AttnGeom& g, int heads, int dim_head,
@@ -518,8 +496,8 @@ bool temporal64_x3(hipStream_t s, const View& x, const View& out, const AttnGeom
     return bf16 ? dispatch<32, true>(s, x, out, g, gamma, ln_w, ln_b, wpk, wsc, mbias, rcos, rsin, q_scale)
                 : dispatch<32, false>(s, x, out, g, gamma, ln_w, ln_b, wpk, wsc, mbias, rcos, rsin, q_scale);
   }
-  return bf16 ? dispatch<16, true>(s, x, out, g, gamma, ln_w, ln_b, wpk, wsc, mbias, rcos, rsin, q_scale)
-              : dispatch<16, false>(s, x, out, g, gamma, ln_w, ln_b, wpk, wsc, mbias, rcos, rsin, q_scale);
+  // BF16_ATTN at dim_head 16 is not this kernel's: temporal_long() sends it to the fp32 route
+  return !bf16 && dispatch<16, false>(s, x, out, g, gamma, ln_w, ln_b, wpk, wsc, mbias, rcos, rsin, q_scale);
 }
 
 }  // namespace extdm
