@@ -6,6 +6,8 @@ Import with importlib (the directory name is not a Python identifier):
 from . import spec, weights, configs, dist, metrics, _lib  # noqa: F401
 from .models import (Unet3D, Unet3DAda, Unet3DAdaU22, Unet3DWoRef, UNET3D_BY_MODULE, GaussianDiffusion,  # noqa: F401
                      schedule_buffers, ddim_time_pairs)
+from .metrics import (InceptionI3d, load_i3d_pretrained, get_feats, get_fvd_feats, calculate_fvd,  # noqa: F401
+                      calculate_fvd1, calculate_fvd2)
 from .lfae import (Generator, RegionPredictor, BGMotionPredictor, FlowDiffusion,  # noqa: F401
                    FlowDiffusionMultiWRef, FlowDiffusionMultiWRefU22, FlowDiffusionMulti1248,
                    FLOW_DIFFUSION_BY_MODULE, autoregressive_sample)

@@ -13,7 +13,10 @@ EXPORTS = ['extdm_create', 'extdm_destroy', 'extdm_last_error', 'extdm_load_weig
            'extdm_decode', 'extdm_set_lfae', 'extdm_region_params', 'extdm_region_hw', 'extdm_bg_params',
            'extdm_flow_predict', 'extdm_flow_hw', 'extdm_bottleneck', 'extdm_range_flag',
            'extdm_attn_layer', 'extdm_frame_metrics_workspace', 'extdm_frame_metrics', 'extdm_bilinear_frames',
-           'extdm_sampler_step_t', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum']
+           'extdm_sampler_step_t', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum',
+           'extdm_fvd_create', 'extdm_fvd_destroy', 'extdm_fvd_load_weight', 'extdm_fvd_finalize',
+           'extdm_fvd_preprocess', 'extdm_fvd_features', 'extdm_fvd_endpoint', 'extdm_fvd_endpoint_shape',
+           'extdm_fvd_range_flag', 'extdm_fvd_same_pad', 'extdm_fvd_maxpool']
 # ... and the declared symbols whose names hold a digit: tests/test_abi.py scans the header for
 # lower-case names only, so they are listed apart (tests/test_teacher_cpu.py checks them)
 EXPORTS_DIGIT = ['extdm_x0_loss']
@@ -126,6 +129,28 @@ def load():
     L.extdm_abs_diff_chunks.restype = i32
     L.extdm_abs_diff_sum.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     L.extdm_abs_diff_sum.restype = i32
+    L.extdm_fvd_create.argtypes = [i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.extdm_fvd_create.restype = i32
+    L.extdm_fvd_destroy.argtypes = [vp]
+    L.extdm_fvd_destroy.restype = None
+    L.extdm_fvd_load_weight.argtypes = [vp, ctypes.c_char_p, vp, i32, ctypes.POINTER(i64), i32]
+    L.extdm_fvd_load_weight.restype = i32
+    L.extdm_fvd_finalize.argtypes = [vp]
+    L.extdm_fvd_finalize.restype = i32
+    L.extdm_fvd_preprocess.argtypes = [vp, i32, i32, i32, i32, i32, lg, lg, lg, i32, i32, vp, vp]
+    L.extdm_fvd_preprocess.restype = i32
+    L.extdm_fvd_features.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L.extdm_fvd_features.restype = i32
+    L.extdm_fvd_endpoint.argtypes = [vp, i32, i32, i32, i32, vp, ctypes.c_char_p, vp, vp]
+    L.extdm_fvd_endpoint.restype = i32
+    L.extdm_fvd_endpoint_shape.argtypes = [vp, i32, i32, i32, ctypes.c_char_p, ctypes.POINTER(i32)]
+    L.extdm_fvd_endpoint_shape.restype = i32
+    L.extdm_fvd_range_flag.argtypes = [vp, i32, vp]
+    L.extdm_fvd_range_flag.restype = i32
+    L.extdm_fvd_same_pad.argtypes = [i32, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32)]
+    L.extdm_fvd_same_pad.restype = i32
+    L.extdm_fvd_maxpool.argtypes = [vp] + [i32] * 11 + [vp, vp]
+    L.extdm_fvd_maxpool.restype = i32
     _lib = L
     return L
 
@@ -411,3 +436,80 @@ class Handle:
         T, fh, fw = flow.shape[2], flow.shape[3], flow.shape[4]
         check(load().extdm_decode(self.h, B, C, T, S, fh, fw, _ptr(ref), _ptr(flow), _ptr(occ), _ptr(out),
                                   _ptr(warped), _stream()))
+
+
+def fvd_preprocess(videos, sequence_length=None, resolution=224):
+    """trans + preprocess_single of every video in one launch (extdm_fvd_preprocess): fp32 device
+    [B, T, C, H, W] in [0, 1] with contiguous planes, C in {1, 3} -> [B, 3, T', resolution,
+    resolution] in [-1, 1]."""
+    import torch
+    if not videos.is_cuda:
+        raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
+    if videos.dim() != 5 or videos.dtype != torch.float32 or videos.stride(-1) != 1 or \
+            videos.stride(-2) != videos.shape[-1]:
+        raise ValueError('fvd_preprocess: fp32 [B, T, C, H, W] with contiguous planes expected')
+    B, T, C, H, W = videos.shape
+    if C not in (1, 3):
+        raise ValueError('fvd_preprocess: 1 or 3 channels expected')
+    if sequence_length is not None and sequence_length > T:
+        raise AssertionError('sequence_length exceeds the clip')  # fvd.py:167
+    To = T if sequence_length is None else int(sequence_length)
+    out = torch.empty(B, 3, To, resolution, resolution, device=videos.device, dtype=torch.float32)
+    with torch.cuda.device(videos.device):
+        check(load().extdm_fvd_preprocess(_ptr(videos), B, T, C, H, W, *videos.stride()[:3], To, resolution,
+                                          _ptr(out), _stream()))
+    return out
+
+
+class FvdHandle:
+    """One native InceptionI3d instance (include/extdm.h, extdm_fvd_*)."""
+
+    def __init__(self, num_classes, in_channels, max_batch, max_frames, device=0):
+        h = ctypes.c_void_p()
+        check(load().extdm_fvd_create(num_classes, in_channels, max_batch, max_frames, device, ctypes.byref(h)))
+        self.h = h
+        self.num_classes, self.in_channels = num_classes, in_channels
+        self.max_batch, self.max_frames = max_batch, max_frames
+
+    def __del__(self):
+        if getattr(self, 'h', None) and _lib is not None:
+            _lib.extdm_fvd_destroy(self.h)
+            self.h = None
+
+    def load_state(self, sd):
+        """sd: reference state_dict key -> tensor."""
+        import torch
+        L = load()
+        for name, t in sd.items():
+            t = t.detach().to('cpu').contiguous()
+            if t.dtype == torch.int64:
+                dt = 1
+            else:
+                t = t.to(torch.float32)
+                dt = 0
+            shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
+            check(L.extdm_fvd_load_weight(self.h, name.encode(), ctypes.c_void_p(t.data_ptr()), dt, shape, t.dim()))
+
+    def finalize(self):
+        check(load().extdm_fvd_finalize(self.h))
+
+    def features(self, x, logits=None, pooled=None):
+        _require_device(x, logits, pooled)
+        check(load().extdm_fvd_features(self.h, x.shape[0], x.shape[2], _ptr(x), _ptr(logits), _ptr(pooled),
+                                        _stream()))
+
+    def endpoint_shape(self, T, H, W, name):
+        d = (ctypes.c_int * 4)()
+        check(load().extdm_fvd_endpoint_shape(self.h, T, H, W, name.encode(), d))
+        return tuple(d)
+
+    def endpoint(self, x, name, out):
+        _require_device(x, out)
+        N, _, T, H, W = x.shape
+        check(load().extdm_fvd_endpoint(self.h, N, T, H, W, _ptr(x), name.encode(), _ptr(out), _stream()))
+
+    def range_flag(self, reset=True):
+        rc = load().extdm_fvd_range_flag(self.h, 1 if reset else 0, _stream())
+        if rc < 0:
+            check(rc)
+        return rc

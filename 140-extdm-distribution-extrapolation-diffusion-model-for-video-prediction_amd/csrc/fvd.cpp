@@ -1,0 +1,466 @@
+// The FVD feature network's runtime: an InceptionI3d (metrics/pytorch_i3d.py:135-322) handle of
+// its own -- weight registry under the reference's state_dict keys, f16x3 packing with the
+// BatchNorm3d folded into a per-channel scale / shift, a workspace planned at
+// max_batch x max_frames x 224^2, the forward as a sequence of i3d.hip launches -- and the
+// extdm_fvd_* part of the C ABI (include/extdm.h).
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <unordered_map>
+#include <vector>
+
+#include "extdm.h"
+#include "i3d.h"
+
+using namespace extdm;
+
+namespace {
+
+struct Error : std::runtime_error {
+  using std::runtime_error::runtime_error;
+};
+
+#define HIPCHK(x)                                                                          \
+  do {                                                                                     \
+    hipError_t e_ = (x);                                                                   \
+    if (e_ != hipSuccess)                                                                  \
+      throw Error(std::string(#x) + " failed: " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
+  } while (0)
+
+#define REQUIRE(c, msg) \
+  do {                  \
+    if (!(c)) throw Error(msg); \
+  } while (0)
+
+struct HostW {
+  std::vector<float> f;
+  std::vector<int64_t> shape;
+};
+
+// pytorch_i3d.py:151-170 up to Mixed_5c (the head follows)
+const char* const kEndpoints[] = {"Conv3d_1a_7x7", "MaxPool3d_2a_3x3", "Conv3d_2b_1x1", "Conv3d_2c_3x3",
+                                  "MaxPool3d_3a_3x3", "Mixed_3b", "Mixed_3c", "MaxPool3d_4a_3x3",
+                                  "Mixed_4b", "Mixed_4c", "Mixed_4d", "Mixed_4e",
+                                  "Mixed_4f", "MaxPool3d_5a_2x2", "Mixed_5b", "Mixed_5c"};
+constexpr int kNumEndpoints = 16;
+// InceptionModule channel tables (pytorch_i3d.py:229-272): in, then out_channels[0..5]
+struct MixedCfg { const char* name; int in, o[6]; };
+const MixedCfg kMixed[] = {{"Mixed_3b", 192, {64, 96, 128, 16, 32, 32}},   {"Mixed_3c", 256, {128, 128, 192, 32, 96, 64}},
+                           {"Mixed_4b", 480, {192, 96, 208, 16, 48, 64}},  {"Mixed_4c", 512, {160, 112, 224, 24, 64, 64}},
+                           {"Mixed_4d", 512, {128, 128, 256, 24, 64, 64}}, {"Mixed_4e", 512, {112, 144, 288, 32, 64, 64}},
+                           {"Mixed_4f", 528, {256, 160, 320, 32, 128, 128}}, {"Mixed_5b", 832, {256, 160, 320, 32, 128, 128}},
+                           {"Mixed_5c", 832, {384, 192, 384, 48, 128, 128}}};
+
+struct Unit {
+  Conv3dW w;
+  const float* scale = nullptr;  // folded BatchNorm3d
+  const float* shift = nullptr;
+};
+
+enum Slot { SX0 = 0, SX1 = 1, ST1 = 2, ST2 = 3, ST3 = 4, SPOOL = 5, NSLOT = 6 };
+
+template <class F>
+int guarded(F&& f) {
+  try {
+    f();
+    return 0;
+  } catch (const std::exception& e) {
+    set_last_error(e.what());
+    return -1;
+  }
+}
+
+}  // namespace
+
+struct ExtdmFvdHandle {
+  int num_classes = 400, in_channels = 3, max_batch = 1, max_frames = 16, device = 0;
+  std::unordered_map<std::string, HostW> host;
+  std::unordered_map<std::string, Unit> units;
+  std::vector<void*> allocations;
+  bool finalized = false;
+  const float* logits_wt = nullptr;  // [1024][num_classes]
+  const float* logits_b = nullptr;
+  int* range = nullptr;
+  // workspace: two ping-pong activations, the three branch temporaries of a module, the pooled head
+  float* slot[NSLOT] = {};
+  size_t cap[NSLOT] = {};
+  bool plan = false;
+  hipStream_t s = nullptr;
+
+  void* dmalloc(size_t bytes) {
+    void* p = nullptr;
+    HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 256)));
+    allocations.push_back(p);
+    return p;
+  }
+  template <class T>
+  T* upload(const std::vector<T>& v) {
+    T* d = reinterpret_cast<T*>(dmalloc(v.size() * sizeof(T)));
+    HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  const HostW& H(const std::string& n) const {
+    auto it = host.find(n);
+    if (it == host.end()) throw Error("missing weight: " + n);
+    return it->second;
+  }
+  const HostW& H(const std::string& n, const std::vector<int64_t>& shape) const {
+    const HostW& t = H(n);
+    if (t.shape != shape) {
+      std::string got, want;
+      for (auto d : t.shape) got += std::to_string(d) + " ";
+      for (auto d : shape) want += std::to_string(d) + " ";
+      throw Error("weight " + n + ": shape [ " + got + "], expected [ " + want + "]");
+    }
+    return t;
+  }
+
+  // Unit3D (pytorch_i3d.py:37-103) `name`: conv3d.weight [M][Cin][KS]^3 packed for conv3d_x3_kernel
+  // ([mtile][ktile][step][m32][hi|lo][lane][8], row m = mtile * BM + m32 * 32 + (lane & 31),
+  // k = ktile * 32 + step * 16 + 8 * (lane >> 5) + e = tap * Cpad + ci; row m scaled by 2^s(m) so
+  // that max |w| lies in [2^14, 2^15), undone by wscale[m]), bn.* folded into scale / shift.
+  void pack_unit(const std::string& name, int M, int Cin, int KS) {
+    const HostW& wt = H(name + ".conv3d.weight", {M, Cin, KS, KS, KS});
+    // the 3-channel stem packs (kt, ky) rows of 7 kx * 3 ci = 21 elements padded to 24 (i3d.hip STEM)
+    const bool stem = KS == 7 && Cin == 3 && M == 64;
+    const int KK = KS * KS * KS, Cpad = (Cin + 7) / 8 * 8, K = stem ? 49 * kStemRow : KK * Cpad;
+    const int bm = conv3d_bm(M), nkt = (K + 31) / 32, mt = (M + bm - 1) / bm, m32 = bm / 32;
+    const size_t ah = (size_t)2 * m32 * 2 * 512;
+    std::vector<float> scale(M), rs(M);
+    for (int m = 0; m < M; ++m) {
+      float mx = 0.f;
+      for (size_t k = 0; k < (size_t)Cin * KK; ++k) mx = std::max(mx, std::fabs(wt.f[(size_t)m * Cin * KK + k]));
+      int e = 0;
+      if (mx > 0.f) { std::frexp(mx, &e); e = 15 - e; }
+      scale[m] = std::ldexp(1.f, e);
+      rs[m] = std::ldexp(1.f, -e);
+    }
+    std::vector<_Float16> g((size_t)mt * nkt * ah, (_Float16)0.f);
+    for (int mtile = 0; mtile < mt; ++mtile)
+      for (int kt = 0; kt < nkt; ++kt)
+        for (int st = 0; st < 2; ++st)
+          for (int q = 0; q < m32; ++q)
+            for (int l = 0; l < 64; ++l)
+              for (int e = 0; e < 8; ++e) {
+                const int m = mtile * bm + q * 32 + (l & 31), k = kt * 32 + st * 16 + 8 * (l >> 5) + e;
+                if (m >= M || k >= K) continue;
+                int tap = k / Cpad, ci = k - tap * Cpad;
+                if (stem) {
+                  const int row = k / kStemRow, j = k - row * kStemRow;
+                  if (j >= 21) continue;
+                  tap = row * 7 + j / 3;
+                  ci = j % 3;
+                }
+                if (ci >= Cin) continue;
+                const float v = wt.f[((size_t)m * Cin + ci) * KK + tap] * scale[m];
+                const _Float16 hi = (_Float16)v;
+                const size_t base = ((size_t)mtile * nkt + kt) * ah + (size_t)((st * m32 + q) * 2) * 512;
+                g[base + l * 8 + e] = hi;
+                g[base + 512 + l * 8 + e] = (_Float16)(v - (float)hi);
+              }
+    Unit u;
+    u.w.w = upload(g);
+    u.w.wscale = upload(rs);
+    u.w.M = M; u.w.Cin = Cin; u.w.Cpad = Cpad; u.w.KS = KS; u.w.bm = bm; u.w.nkt = nkt; u.w.stem = stem;
+    // BatchNorm3d (eval, eps 1e-5; pytorch_i3d.py:69): y = x * sc + sh, computed in fp64
+    const HostW& bw = H(name + ".bn.weight", {M});
+    const HostW& bb = H(name + ".bn.bias", {M});
+    const HostW& bmn = H(name + ".bn.running_mean", {M});
+    const HostW& bv = H(name + ".bn.running_var", {M});
+    std::vector<float> sc(M), sh(M);
+    for (int m = 0; m < M; ++m) {
+      const double s_ = (double)bw.f[m] / std::sqrt((double)bv.f[m] + 1e-5);
+      sc[m] = (float)s_;
+      sh[m] = (float)((double)bb.f[m] - (double)bmn.f[m] * s_);
+    }
+    u.scale = upload(sc);
+    u.shift = upload(sh);
+    units[name] = u;
+  }
+
+  void finalize() {
+    REQUIRE(!finalized, "already finalized");
+    HIPCHK(hipSetDevice(device));
+    pack_unit("Conv3d_1a_7x7", 64, in_channels, 7);
+    pack_unit("Conv3d_2b_1x1", 64, 64, 1);
+    pack_unit("Conv3d_2c_3x3", 192, 64, 3);
+    for (const MixedCfg& m : kMixed) {
+      const std::string p = std::string(m.name) + ".";
+      pack_unit(p + "b0", m.o[0], m.in, 1);
+      pack_unit(p + "b1a", m.o[1], m.in, 1);
+      pack_unit(p + "b1b", m.o[2], m.o[1], 3);
+      pack_unit(p + "b2a", m.o[3], m.in, 1);
+      pack_unit(p + "b2b", m.o[4], m.o[3], 3);
+      pack_unit(p + "b3b", m.o[5], m.in, 1);
+    }
+    const int K = num_classes;
+    const HostW& lw = H("logits.conv3d.weight", {K, 1024, 1, 1, 1});
+    const HostW& lb = H("logits.conv3d.bias", {K});
+    std::vector<float> wt((size_t)1024 * K);
+    for (int k = 0; k < K; ++k)
+      for (int c = 0; c < 1024; ++c) wt[(size_t)c * K + k] = lw.f[(size_t)k * 1024 + c];
+    logits_wt = upload(wt);
+    logits_b = upload(lb.f);
+    range = reinterpret_cast<int*>(dmalloc(sizeof(int)));
+    HIPCHK(hipMemset(range, 0, sizeof(int)));
+    // plan the workspace with a dry run at the largest launch
+    plan = true;
+    int dims[4];
+    run(max_batch, max_frames, 224, 224, nullptr, kNumEndpoints - 1, dims);
+    need(SPOOL, (size_t)max_batch * 1024 * std::max(1, dims[1] - 1));
+    plan = false;
+    for (int i = 0; i < NSLOT; ++i) slot[i] = reinterpret_cast<float*>(dmalloc(cap[i] * sizeof(float)));
+    host.clear();
+    finalized = true;
+  }
+
+  float* need(int sl, size_t nfloat) {
+    if (plan) {
+      cap[sl] = std::max(cap[sl], nfloat);
+      return nullptr;
+    }
+    REQUIRE(nfloat <= cap[sl], "fvd: workspace overflow (batch, frames or size beyond max_batch x max_frames x 224^2)");
+    return slot[sl];
+  }
+
+  Vol vol(float* p, int B, int C, int T, int Hh, int W) const {
+    Vol v; v.p = p; v.B = B; v.C = C; v.T = T; v.H = Hh; v.W = W;
+    v.sc = (long)T * Hh * W; v.sb = (long)C * v.sc; return v;
+  }
+
+  // Unit3D into channels [c0, c0 + M) of the contiguous activation `out` of Ctot channels
+  void unit(const std::string& name, const Vol& in, float* out, int Ctot, int c0, int stride) {
+    if (plan) return;
+    const Unit& u = units.at(name);
+    const int To = same_out(in.T, stride), Ho = same_out(in.H, stride), Wo = same_out(in.W, stride);
+    const long thw = (long)To * Ho * Wo;
+    REQUIRE(conv3d_x3_forward(s, in, u.w, stride, out + (long)c0 * thw, (long)Ctot * thw, thw, (long)Ho * Wo, u.scale,
+                              u.shift, true, range),
+            "fvd: convolution " + name + " not covered (activation larger than 4 GiB?)");
+  }
+
+  // The network from the input up to and including endpoint `last` (index into kEndpoints).
+  // Returns the activation (slot memory) and its dims {C, T, H, W}.
+  float* run(int N, int T, int Hh, int W, const float* x, int last, int dims[4]) {
+    Vol cur = vol(const_cast<float*>(x), N, in_channels, T, Hh, W);
+    int pp = 0;  // next ping-pong slot
+    auto next = [&](int C, int To, int Ho, int Wo) {
+      float* p = need(pp, (size_t)N * C * To * Ho * Wo);
+      pp ^= 1;
+      return vol(p, N, C, To, Ho, Wo);
+    };
+    auto conv = [&](const char* name, int M, int stride) {
+      Vol o = next(M, same_out(cur.T, stride), same_out(cur.H, stride), same_out(cur.W, stride));
+      unit(name, cur, o.p, M, 0, stride);
+      cur = o;
+    };
+    auto pool = [&](int kt, int kh, int kw, int st, int sh, int sw) {
+      Vol o = next(cur.C, same_out(cur.T, st), same_out(cur.H, sh), same_out(cur.W, sw));
+      if (!plan) REQUIRE(maxpool3d_same(s, cur, o.p, kt, kh, kw, st, sh, sw), "fvd: max pool grid too large");
+      cur = o;
+    };
+    auto mixed = [&](const MixedCfg& m) {
+      const std::string p = std::string(m.name) + ".";
+      const int Ct = m.o[0] + m.o[2] + m.o[4] + m.o[5];
+      Vol o = next(Ct, cur.T, cur.H, cur.W);
+      const size_t thw = (size_t)N * cur.thw();
+      Vol t1 = vol(need(ST1, thw * m.o[1]), N, m.o[1], cur.T, cur.H, cur.W);
+      Vol t2 = vol(need(ST2, thw * m.o[3]), N, m.o[3], cur.T, cur.H, cur.W);
+      Vol t3 = vol(need(ST3, thw * m.in), N, m.in, cur.T, cur.H, cur.W);
+      // the four branches write their channel slices of the module's output (pytorch_i3d.py:127-132)
+      unit(p + "b0", cur, o.p, Ct, 0, 1);
+      unit(p + "b1a", cur, t1.p, m.o[1], 0, 1);
+      unit(p + "b1b", t1, o.p, Ct, m.o[0], 1);
+      unit(p + "b2a", cur, t2.p, m.o[3], 0, 1);
+      unit(p + "b2b", t2, o.p, Ct, m.o[0] + m.o[2], 1);
+      if (!plan) REQUIRE(maxpool3d_same(s, cur, t3.p, 3, 3, 3, 1, 1, 1), "fvd: max pool grid too large");
+      unit(p + "b3b", t3, o.p, Ct, m.o[0] + m.o[2] + m.o[4], 1);
+      cur = o;
+    };
+    int mi = 0;
+    for (int ep = 0; ep <= last; ++ep) {
+      switch (ep) {
+        case 0: conv("Conv3d_1a_7x7", 64, 2); break;
+        case 1: case 4: pool(1, 3, 3, 1, 2, 2); break;
+        case 2: conv("Conv3d_2b_1x1", 64, 1); break;
+        case 3: conv("Conv3d_2c_3x3", 192, 1); break;
+        case 7: pool(3, 3, 3, 2, 2, 2); break;
+        case 13: pool(2, 2, 2, 2, 2, 2); break;
+        default: mixed(kMixed[mi++]); break;
+      }
+    }
+    dims[0] = cur.C; dims[1] = cur.T; dims[2] = cur.H; dims[3] = cur.W;
+    return cur.p;
+  }
+
+  int endpoint_index(const char* name) const {
+    for (int i = 0; i < kNumEndpoints; ++i)
+      if (!strcmp(name, kEndpoints[i])) return i;
+    throw Error(std::string("fvd: unknown endpoint ") + name);
+  }
+};
+
+extern "C" {
+
+int extdm_fvd_create(int num_classes, int in_channels, int max_batch, int max_frames, int device,
+                     ExtdmFvdHandle** out) {
+  return guarded([&] {
+    REQUIRE(out, "null argument");
+    REQUIRE(num_classes >= 1 && in_channels >= 1 && max_batch >= 1, "fvd: bad configuration");
+    REQUIRE(max_frames >= 9, "fvd: InceptionI3d needs at least 9 frames");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    REQUIRE(ndev > 0, "no HIP device visible");
+    REQUIRE(device >= 0 && device < ndev, "fvd: no such device");
+    auto h = std::make_unique<ExtdmFvdHandle>();
+    h->num_classes = num_classes; h->in_channels = in_channels;
+    h->max_batch = max_batch; h->max_frames = max_frames; h->device = device;
+    *out = h.release();
+  });
+}
+
+void extdm_fvd_destroy(ExtdmFvdHandle* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->device);
+  (void)hipDeviceSynchronize();
+  for (void* p : h->allocations) (void)hipFree(p);
+  delete h;
+}
+
+int extdm_fvd_load_weight(ExtdmFvdHandle* h, const char* name, const void* ptr, int dtype, const int64_t* shape,
+                          int ndim) {
+  return guarded([&] {
+    REQUIRE(h && name && ptr, "null argument");
+    REQUIRE(!h->finalized, "weights are frozen after extdm_fvd_finalize");
+    const size_t len = strlen(name);
+    if (len >= 19 && !strcmp(name + len - 19, "num_batches_tracked")) return;  // accepted, not used
+    REQUIRE(dtype == 0, "fvd: float32 weights expected: " + std::string(name));
+    HostW t;
+    size_t n = 1;
+    for (int i = 0; i < ndim; ++i) { t.shape.push_back(shape[i]); n *= (size_t)shape[i]; }
+    t.f.assign(reinterpret_cast<const float*>(ptr), reinterpret_cast<const float*>(ptr) + n);
+    h->host[name] = std::move(t);
+  });
+}
+
+int extdm_fvd_finalize(ExtdmFvdHandle* h) {
+  return guarded([&] {
+    REQUIRE(h, "null handle");
+    h->finalize();
+  });
+}
+
+int extdm_fvd_preprocess(const float* in, int B, int T, int C, int H, int W, long sb, long st, long sc,
+                         int sequence_length, int resolution, float* out, void* stream) {
+  return guarded([&] {
+    REQUIRE(in && out, "fvd_preprocess: null pointer");
+    REQUIRE(B > 0 && T > 0 && (C == 1 || C == 3) && H > 0 && W > 0 && resolution > 0, "fvd_preprocess: bad geometry");
+    REQUIRE(sequence_length <= T, "fvd_preprocess: sequence_length exceeds the clip");  // fvd.py:167
+    const int To = sequence_length > 0 ? sequence_length : T;
+    // fvd.py:171-175 in the reference's double arithmetic
+    const double scale = (double)resolution / (double)std::min(H, W);
+    int Hr = resolution, Wr = resolution;
+    if (H < W) Wr = (int)std::ceil((double)W * scale);
+    else Hr = (int)std::ceil((double)H * scale);
+    fvd_preprocess(reinterpret_cast<hipStream_t>(stream), in, sb, st, sc, B, C, To, H, W, Hr, Wr,
+                   (Hr - resolution) / 2, (Wr - resolution) / 2, resolution, out);
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_fvd_maxpool(const float* x, int B, int C, int T, int H, int W, int kt, int kh, int kw, int st, int sh,
+                      int sw, float* out, void* stream) {
+  return guarded([&] {
+    REQUIRE(x && out, "fvd_maxpool: null pointer");
+    REQUIRE(B > 0 && C > 0 && T > 0 && H > 0 && W > 0 && kt > 0 && kh > 0 && kw > 0 && st > 0 && sh > 0 && sw > 0,
+            "fvd_maxpool: bad geometry");
+    Vol v; v.p = const_cast<float*>(x); v.B = B; v.C = C; v.T = T; v.H = H; v.W = W;
+    v.sc = (long)T * H * W; v.sb = (long)C * v.sc;
+    REQUIRE(maxpool3d_same(reinterpret_cast<hipStream_t>(stream), v, out, kt, kh, kw, st, sh, sw),
+            "fvd_maxpool: not covered (windows [1,3,3], [3,3,3], [2,2,2]; C * T' and B at most 65535)");
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_fvd_same_pad(int size, int kernel, int stride, int* front, int* back) {
+  if (size < 1 || kernel < 1 || stride < 1) return -1;
+  const int p = same_pad(size, kernel, stride);
+  if (front) *front = p / 2;
+  if (back) *back = p - p / 2;
+  return same_out(size, stride);
+}
+
+int extdm_fvd_endpoint_shape(const ExtdmFvdHandle* h, int T, int H, int W, const char* endpoint_name, int* dims) {
+  return guarded([&] {
+    REQUIRE(h && endpoint_name && dims, "null argument");
+    REQUIRE(T >= 1 && H >= 1 && W >= 1, "fvd: bad geometry");
+    ExtdmFvdHandle tmp;  // a planning walk: no launches, no allocation
+    tmp.in_channels = h->in_channels;
+    tmp.plan = true;
+    tmp.run(1, T, H, W, nullptr, h->endpoint_index(endpoint_name), dims);
+  });
+}
+
+int extdm_fvd_endpoint(ExtdmFvdHandle* h, int N, int T, int H, int W, const float* x, const char* endpoint_name,
+                       float* out, void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "fvd: handle not finalized");
+    REQUIRE(x && out && endpoint_name, "null argument");
+    REQUIRE(N >= 1 && T >= 1 && H >= 1 && W >= 1, "fvd: bad geometry");
+    HIPCHK(hipSetDevice(h->device));
+    h->s = reinterpret_cast<hipStream_t>(stream);
+    int d[4];
+    const float* y = h->run(N, T, H, W, x, h->endpoint_index(endpoint_name), d);
+    HIPCHK(hipMemcpyAsync(out, y, (size_t)N * d[0] * d[1] * d[2] * d[3] * sizeof(float), hipMemcpyDeviceToDevice,
+                          h->s));
+    HIPCHK(hipGetLastError());
+  });
+}
+
+int extdm_fvd_features(ExtdmFvdHandle* h, int N, int T, const float* x, float* logits_out, float* pooled_out,
+                       void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "fvd: handle not finalized");
+    REQUIRE(x && (logits_out || pooled_out), "null argument");
+    REQUIRE(N >= 1 && N <= h->max_batch, "fvd: batch exceeds max_batch");
+    // the head's AvgPool3d([2, 7, 7]) needs two time slots: T -> ceil(T/2) three times >= 2
+    REQUIRE(T >= 9, "fvd: InceptionI3d needs at least 9 frames, got " + std::to_string(T));
+    REQUIRE(T <= h->max_frames, "fvd: clip longer than max_frames");
+    HIPCHK(hipSetDevice(h->device));
+    h->s = reinterpret_cast<hipStream_t>(stream);
+    HIPCHK(hipMemsetAsync(h->range, 0, sizeof(int), h->s));
+    int d[4];
+    const float* y = h->run(N, T, 224, 224, x, kNumEndpoints - 1, d);
+    const int S = d[1] - 1;
+    float* pooled = h->need(SPOOL, (size_t)N * 1024 * S);
+    i3d_avgpool(h->s, y, pooled, N, 1024, d[1]);
+    if (pooled_out)
+      HIPCHK(hipMemcpyAsync(pooled_out, pooled, (size_t)N * 1024 * S * sizeof(float), hipMemcpyDeviceToDevice, h->s));
+    if (logits_out) i3d_logits(h->s, pooled, h->logits_wt, h->logits_b, logits_out, N, 1024, S, h->num_classes);
+    HIPCHK(hipGetLastError());
+    int flag = 0;
+    HIPCHK(hipMemcpyAsync(&flag, h->range, sizeof(int), hipMemcpyDeviceToHost, h->s));
+    HIPCHK(hipStreamSynchronize(h->s));
+    REQUIRE(flag == 0, "fvd: activation out of fp16 range (|v| >= 65504) in an f16x3 convolution");
+  });
+}
+
+int extdm_fvd_range_flag(ExtdmFvdHandle* h, int reset, void* stream) {
+  int flag = 0;
+  const int rc = guarded([&] {
+    REQUIRE(h && h->finalized, "fvd: handle not finalized");
+    HIPCHK(hipSetDevice(h->device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    HIPCHK(hipMemcpyAsync(&flag, h->range, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (reset) HIPCHK(hipMemsetAsync(h->range, 0, sizeof(int), s));
+    HIPCHK(hipStreamSynchronize(s));
+  });
+  return rc != 0 ? rc : flag;
+}
+
+}  // extern "C"

@@ -1,0 +1,66 @@
+// InceptionI3d (the FVD feature network, metrics/pytorch_i3d.py) -- kernels of i3d.hip and the
+// pieces fvd.cpp shares with runtime.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <string>
+
+namespace extdm {
+
+// TF-style 'same' padding of Unit3D / MaxPool3dSamePadding (pytorch_i3d.py:9-13, 71-95) for one
+// dimension of extent `size`: the total pad; front = pad / 2, back = the rest.
+inline int same_pad(int size, int k, int stride) {
+  const int r = size % stride;
+  const int p = r == 0 ? k - stride : k - r;
+  return p > 0 ? p : 0;
+}
+inline int same_out(int size, int stride) { return (size + stride - 1) / stride; }
+
+// A channel-first activation [B][C][T][H][W] with contiguous T*H*W volumes per channel.
+struct Vol {
+  float* p = nullptr;
+  int B = 0, C = 0, T = 0, H = 0, W = 0;
+  long sb = 0, sc = 0;  // batch / channel strides in elements
+  long thw() const { return (long)T * H * W; }
+};
+
+// f16x3 packing of a Unit3D weight [M][Cin][KS][KS][KS] (i3d.hip header): tap-major K with the
+// input channels padded to a multiple of 8, rows pre-scaled by powers of two undone by wscale[m].
+// stem: the 3-channel 7x7x7 unit's row-major K instead, k = (kt * 7 + ky) * 24 + kx * 3 + ci;
+// M = 64 only.
+struct Conv3dW {
+  const void* w = nullptr;
+  const float* wscale = nullptr;
+  int M = 0, Cin = 0, Cpad = 0, KS = 1, bm = 0, nkt = 0;
+  bool stem = false;
+};
+constexpr int kStemRow = 24;  // 7 kx * 3 ci = 21 elements of a (kt, ky) row, padded to three groups of 8
+inline int conv3d_bm(int M) { return M <= 32 ? 32 : (M % 128 == 0 ? 128 : 64); }
+
+// out[b][m][to][oy][ox] (through ob / oc / ot strides, planes contiguous) =
+//   act(conv3d_same(in, w, stride)[m] * post_scale[m] + post_shift[m])
+// post_scale null: no affine. False if the launch is not covered (offsets past 32 bits).
+bool conv3d_x3_forward(hipStream_t s, const Vol& in, const Conv3dW& w, int stride, float* out, long ob, long oc,
+                       long ot, const float* post_scale, const float* post_shift, bool relu, int* range);
+
+// MaxPool3dSamePadding (pytorch_i3d.py:15-34): zero padding, then the max; out contiguous
+// [B][C][To][Ho][Wo]. False if not covered: a window other than [1,3,3], [3,3,3], [2,2,2], or
+// C * To or B above 65535.
+bool maxpool3d_same(hipStream_t s, const Vol& in, float* out, int kt, int kh, int kw, int st, int sh, int sw);
+
+// AvgPool3d([2, 7, 7], stride 1) of x [N][C][T][7][7] -> pooled [N][C][T - 1]
+void i3d_avgpool(hipStream_t s, const float* x, float* pooled, int N, int C, int T);
+// logits[n][k] = mean_s (sum_c wt[c][k] pooled[n][c][s] + bias[k]); wt is the logits weight transposed
+void i3d_logits(hipStream_t s, const float* pooled, const float* wt, const float* bias, float* logits, int N, int C,
+                int S, int K);
+
+// trans + preprocess_single (calculate_fvd.py:6-14, fvd.py:161-187): in [B][T][C][H][W] through
+// element strides (planes contiguous) -> out [B][3][To][R][R], bilinear resize of the shorter side
+// to R (resized extents Hr x Wr), centre crop at (y0, x0), (v - 0.5) * 2
+void fvd_preprocess(hipStream_t s, const float* in, long sb, long st, long sc, int B, int C, int To, int H, int W,
+                    int Hr, int Wr, int y0, int x0, int R, float* out);
+
+// the thread's extdm_last_error message (runtime.cpp)
+void set_last_error(const std::string& msg);
+
+}  // namespace extdm

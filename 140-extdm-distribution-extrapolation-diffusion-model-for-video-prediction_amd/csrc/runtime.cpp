@@ -2380,6 +2380,8 @@ int guarded(F&& f) {
 }  // namespace
 
 namespace extdm {
+// the message of extdm_last_error for entry points outside this file (fvd.cpp; declared in i3d.h)
+void set_last_error(const std::string& msg) { g_last_error = msg; }
 static thread_local std::string g_noted_kernel;
 // kernel-name notes are formatted only inside extdm_bench_layer (NoteScope): the forward's
 // launchers call note_kernel on every launch

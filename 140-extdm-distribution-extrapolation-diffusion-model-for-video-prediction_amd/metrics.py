@@ -6,11 +6,16 @@ mean / std / 95 % interval summary.
 Videos follow the reference's metric layout [n, t, c, h, w] (valid.py:194-195 rearranges
 `(b n) c t h w -> b n t c h w`); `frame_metrics` also takes the sampler's channel-first
 [n, c, t, h, w] through `layout='ncthw'`, so generated clips need no transpose. Values
-are in [0, 1] as the reference's (calculate_psnr.py:6-7). LPIPS and the I3D features of
-FVD need network weights the reference does not ship; frechet_distance
-takes the features as given.
+are in [0, 1] as the reference's (calculate_psnr.py:6-7). The I3D features of FVD come
+from `InceptionI3d` (metrics/pytorch_i3d.py, on the native library's 3-D convolution) with
+the mirrored front end of metrics/calculate_fvd.py and fvd.py (`trans`, `preprocess_single`,
+`get_fvd_feats`, `get_feats`, `calculate_fvd*`); the weights are the user's own
+i3d_pretrained_400.pt state_dict (`load_i3d_pretrained`), which the reference does not ship
+either. LPIPS needs a network and a package that are absent: not computed.
 """
 import numpy as np
+import torch
+import torch.nn as nn
 
 from . import _lib
 
@@ -153,15 +158,24 @@ def metric_stuff(metric):
     return avg_metric, std_metric, conf95_metric
 
 
-def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, result_feats=None):
+def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, result_feats=None, i3d=None,
+                 mini_bs=16):
     """The metric half of valid.py:199-257 on [b, n, t, c, h, w] videos: per clip the best of
     its n samples for PSNR and SSIM over the predicted frames (calculate_psnr2 /
-    calculate_ssim2), summarised by metric_stuff. With video features given (origin [b, d],
-    result [b * n, d]; the reference's I3D features, not shipped with it), the best sample
-    per clip by feature L1 (valid.py:234-240) and its frechet_distance to the originals
-    ('fvd_best'), and one frechet_distance per sample trajectory summarised by metric_stuff
-    ('fvd_traj_mean' / '_std' / '_conf95', valid.py:207-213). LPIPS needs network weights
-    the reference does not ship: not computed."""
+    calculate_ssim2), summarised by metric_stuff. With video features (origin [b, d], result
+    [b * n, d]) the best sample per clip by feature L1 (valid.py:234-240) and its
+    frechet_distance to the originals ('fvd_best'), and one frechet_distance per sample
+    trajectory summarised by metric_stuff ('fvd_traj_mean' / '_std' / '_conf95',
+    valid.py:207-213). The features are either given, or computed here by the detector `i3d`
+    (an InceptionI3d with the user's weights, load_i3d_pretrained): origin_feats from
+    origin_videos[:, 0] and result_feats from the `(b n)` flattening (valid.py:203-204), in
+    mini-batches of mini_bs. The reference runs the detector again on the selected videos
+    (valid.py:235); here their rows of result_feats are taken, which is the same thing because
+    a video's features do not depend on its batch. LPIPS needs network weights the reference
+    does not ship: not computed."""
+    if i3d is not None and origin_feats is None and result_feats is None:
+        origin_feats = get_feats(origin_videos[:, 0], origin_videos.device, mini_bs=mini_bs, i3d=i3d)
+        result_feats = get_feats(result_videos.flatten(0, 1), result_videos.device, mini_bs=mini_bs, i3d=i3d)
     psnr_list, ssim_list = best_of_n(origin_videos, result_videos, cond_frames)
     avg_psnr, std_psnr, conf95_psnr = metric_stuff(np.array(psnr_list))
     avg_ssim, std_ssim, conf95_ssim = metric_stuff(np.array(ssim_list))
@@ -178,3 +192,232 @@ def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, r
         fvd_list = [frechet_distance(np.asarray(origin_feats), rf[:, traj]) for traj in range(n)]
         out['fvd_traj_mean'], out['fvd_traj_std'], out['fvd_traj_conf95'] = metric_stuff(np.array(fvd_list))
     return out
+
+
+# ---------------------------------------------------------------- FVD features (I3D)
+class _Unit3D(nn.Module):
+    """Parameter holder of a Unit3D (pytorch_i3d.py:37-69): `conv3d` and, with batch norm, `bn`
+    carry the reference's state_dict entries; the arithmetic runs in the native library."""
+
+    def __init__(self, in_channels, output_channels, kernel_shape=(1, 1, 1), stride=(1, 1, 1), use_batch_norm=True,
+                 use_bias=False):
+        super().__init__()
+        self.conv3d = nn.Conv3d(in_channels, output_channels, tuple(kernel_shape), stride=stride, padding=0,
+                                bias=use_bias)
+        if use_batch_norm:
+            self.bn = nn.BatchNorm3d(output_channels, eps=1e-5, momentum=0.001)
+
+
+class _InceptionModule(nn.Module):
+    """pytorch_i3d.py:107-125 (b3a, the max pool, has no state)."""
+
+    def __init__(self, in_channels, out_channels):
+        super().__init__()
+        self.b0 = _Unit3D(in_channels, out_channels[0])
+        self.b1a = _Unit3D(in_channels, out_channels[1])
+        self.b1b = _Unit3D(out_channels[1], out_channels[2], (3, 3, 3))
+        self.b2a = _Unit3D(in_channels, out_channels[3])
+        self.b2b = _Unit3D(out_channels[3], out_channels[4], (3, 3, 3))
+        self.b3b = _Unit3D(in_channels, out_channels[5])
+
+
+def _need_rocm(x):
+    if not x.is_cuda:
+        raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
+
+
+class InceptionI3d(nn.Module):
+    """Inception-v1 I3D (metrics/pytorch_i3d.py:135-322), the detector of FVD, on the native
+    library: the reference's constructor signature, state_dict keys and shapes (344 entries at
+    the defaults, the public i3d_pretrained_400.pt layout), forward -> [N, num_classes]
+    pre-softmax logits averaged over the time slots, extract_features -> the avg-pooled
+    [N, 1024, T'' - 1, 1, 1], replace_logits. Inference only (dropout is the identity); inputs
+    are [N, in_channels, T >= 9, 224, 224] device tensors. A video's outputs are bitwise
+    independent of the batch it sits in."""
+
+    VALID_ENDPOINTS = ('Conv3d_1a_7x7', 'MaxPool3d_2a_3x3', 'Conv3d_2b_1x1', 'Conv3d_2c_3x3', 'MaxPool3d_3a_3x3',
+                       'Mixed_3b', 'Mixed_3c', 'MaxPool3d_4a_3x3', 'Mixed_4b', 'Mixed_4c', 'Mixed_4d', 'Mixed_4e',
+                       'Mixed_4f', 'MaxPool3d_5a_2x2', 'Mixed_5b', 'Mixed_5c', 'Logits', 'Predictions')
+    _MIXED = (('Mixed_3b', 192, (64, 96, 128, 16, 32, 32)), ('Mixed_3c', 256, (128, 128, 192, 32, 96, 64)),
+              ('Mixed_4b', 480, (192, 96, 208, 16, 48, 64)), ('Mixed_4c', 512, (160, 112, 224, 24, 64, 64)),
+              ('Mixed_4d', 512, (128, 128, 256, 24, 64, 64)), ('Mixed_4e', 512, (112, 144, 288, 32, 64, 64)),
+              ('Mixed_4f', 528, (256, 160, 320, 32, 128, 128)), ('Mixed_5b', 832, (256, 160, 320, 32, 128, 128)),
+              ('Mixed_5c', 832, (384, 192, 384, 48, 128, 128)))
+
+    def __init__(self, num_classes=400, spatial_squeeze=True, final_endpoint='Logits', name='inception_i3d',
+                 in_channels=3, dropout_keep_prob=0.5):
+        if final_endpoint not in self.VALID_ENDPOINTS:
+            raise ValueError('Unknown final endpoint %s' % final_endpoint)
+        if final_endpoint != 'Logits':
+            # the reference returns from __init__ before registering anything (pytorch_i3d.py:207)
+            raise NotImplementedError("only final_endpoint='Logits' is built; InceptionI3d.endpoint() taps the others")
+        super().__init__()
+        self._num_classes = num_classes
+        self._spatial_squeeze = spatial_squeeze
+        self._final_endpoint = final_endpoint
+        self._in_channels = in_channels
+        self.name = name
+        # the reference registers `logits` before the endpoints (pytorch_i3d.py:279-287)
+        self.logits = _Unit3D(1024, num_classes, use_batch_norm=False, use_bias=True)
+        self.add_module('Conv3d_1a_7x7', _Unit3D(in_channels, 64, (7, 7, 7), stride=(2, 2, 2)))
+        self.add_module('Conv3d_2b_1x1', _Unit3D(64, 64))
+        self.add_module('Conv3d_2c_3x3', _Unit3D(64, 192, (3, 3, 3)))
+        for mname, cin, cout in self._MIXED:
+            self.add_module(mname, _InceptionModule(cin, cout))
+        self.eval()
+        self._handle = None
+
+    def replace_logits(self, num_classes):
+        self._num_classes = num_classes
+        dev = self.logits.conv3d.weight.device
+        self.logits = _Unit3D(1024, num_classes, use_batch_norm=False, use_bias=True).to(dev)
+        self._handle = None
+
+    def _state_version(self):
+        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+
+    def _h(self, device, N, T):
+        """Native handle sized for N videos of T frames, rebuilt when the state changes (the
+        mechanism of lfae._NativeModule)."""
+        dev = device.index or 0
+        h = self._handle
+        ver = self._state_version()
+        if h is None or h[0] != dev or h[1] < N or h[2] < T or h[3] != ver:
+            same = h is not None and h[0] == dev
+            N2, T2 = max(N, h[1] if same else 0), max(T, 9, h[2] if same else 0)
+            nh = _lib.FvdHandle(self._num_classes, self._in_channels, N2, T2, dev)
+            nh.load_state(self.state_dict())
+            nh.finalize()
+            self._handle = h = (dev, N2, T2, ver, nh)
+        return h[4]
+
+    def _check(self, x, full):
+        _need_rocm(x)
+        if x.dim() != 5 or x.shape[1] != self._in_channels:
+            raise ValueError(f'InceptionI3d: [N, {self._in_channels}, T, H, W] expected, got {tuple(x.shape)}')
+        if full:
+            if x.shape[2] < 9:
+                # AvgPool3d([2, 7, 7]) needs two time slots after three temporal halvings
+                raise ValueError(f'InceptionI3d needs at least 9 frames, got {x.shape[2]}')
+            if tuple(x.shape[3:]) != (224, 224):
+                raise ValueError(f'InceptionI3d: 224 x 224 frames expected, got {tuple(x.shape[3:])}')
+        return x.float().contiguous()
+
+    def _run(self, x, want_logits):
+        x = self._check(x, True)
+        N, T = x.shape[0], x.shape[2]
+        h = self._h(x.device, N, T)
+        with torch.cuda.device(x.device):
+            if want_logits:
+                out = torch.empty(N, self._num_classes, device=x.device)
+                h.features(x, logits=out)
+                return out
+            S = h.endpoint_shape(T, 224, 224, 'Mixed_5c')[1] - 1
+            out = torch.empty(N, 1024, S, 1, 1, device=x.device)
+            h.features(x, pooled=out)
+            return out
+
+    @torch.no_grad()
+    def forward(self, x):
+        return self._run(x, True)
+
+    @torch.no_grad()
+    def extract_features(self, x):
+        return self._run(x, False)
+
+    @torch.no_grad()
+    def endpoint(self, x, name):
+        """The activation after endpoint `name` (VALID_ENDPOINTS up to Mixed_5c) for an input of
+        any size: the parity hook."""
+        x = self._check(x, False)
+        N, _, T, H, W = x.shape
+        # a handle planned for 224^2 frames holds any smaller input of the same frame count
+        h = self._h(x.device, N, T)
+        with torch.cuda.device(x.device):
+            out = torch.empty(N, *h.endpoint_shape(T, H, W, name), device=x.device)
+            h.endpoint(x, name, out)
+        return out
+
+
+def trans(x):
+    """calculate_fvd.py:6-14: grey -> 3 channels, BTCHW -> BCTHW (a view)."""
+    if x.shape[-3] == 1:
+        x = x.repeat(1, 1, 3, 1, 1)
+    return x.permute(0, 2, 1, 3, 4)
+
+
+def preprocess_single(video, resolution=224, sequence_length=None):
+    """fvd.py:161-187 for one device video [C, T, H, W] in [0, 1] -> [3, T', resolution,
+    resolution] in [-1, 1] (extdm_fvd_preprocess)."""
+    return _lib.fvd_preprocess(video.permute(1, 0, 2, 3)[None], sequence_length, resolution)[0]
+
+
+def _preprocess_bcthw(videos):
+    """preprocess_single of every video of a BCTHW batch in one launch."""
+    v = videos.permute(0, 2, 1, 3, 4)
+    if v.dtype != torch.float32 or v.stride(-1) != 1 or v.stride(-2) != v.shape[-1]:
+        v = v.float().contiguous()
+    return _lib.fvd_preprocess(v)
+
+
+def get_fvd_feats(videos, i3d, device, bs=10):
+    """fvd.py:43-57: videos BCTHW in [0, 1] -> float64 numpy [n, num_classes], the detector's
+    pre-softmax logits, in mini-batches of bs."""
+    feats = np.empty((0, i3d._num_classes))
+    videos = videos.to(device)
+    for i in range((len(videos) - 1) // bs + 1):
+        x = _preprocess_bcthw(videos[i * bs:(i + 1) * bs])
+        feats = np.vstack([feats, i3d(x).detach().cpu().numpy()])
+    return feats
+
+
+_I3D_FILE = 'i3d_pretrained_400.pt'
+
+
+def load_i3d_pretrained(device, path=None):
+    """The detector with the user's weights: a state_dict file in the public
+    i3d_pretrained_400.pt layout (the loader of fvd.py:16-27). `path` defaults to that file
+    name next to this module. Nothing is ever fetched."""
+    import os
+    path = path or os.path.join(os.path.dirname(os.path.abspath(__file__)), _I3D_FILE)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f'I3D weights not found: {path} (expected the InceptionI3d state_dict '
+                                f'{_I3D_FILE}, 400 classes; pass path=... or an i3d=... detector)')
+    i3d = InceptionI3d(400, in_channels=3)
+    i3d.load_state_dict(torch.load(path, map_location='cpu'))
+    return i3d.to(device).eval()
+
+
+def get_feats(videos, device, mini_bs=10, i3d=None):
+    """calculate_fvd.py:61-65: videos BTCHW in [0, 1]."""
+    i3d = i3d if i3d is not None else load_i3d_pretrained(device=device)
+    return get_fvd_feats(trans(videos), i3d=i3d, device=device, bs=mini_bs)
+
+
+def calculate_fvd(videos1, videos2, device, i3d=None):
+    """calculate_fvd.py:16-59: one FVD per clip length from 10 frames upwards."""
+    assert videos1.shape == videos2.shape
+    i3d = i3d if i3d is not None else load_i3d_pretrained(device=device)
+    videos1, videos2 = trans(videos1), trans(videos2)
+    fvd_results = {}
+    for clip_timestamp in range(videos1.shape[-3]):
+        if clip_timestamp < 10:
+            continue
+        feats1 = get_fvd_feats(videos1[:, :, :clip_timestamp], i3d=i3d, device=device)
+        feats2 = get_fvd_feats(videos2[:, :, :clip_timestamp], i3d=i3d, device=device)
+        fvd_results[f'[{clip_timestamp}]'] = frechet_distance(feats1, feats2)
+    return {'fvd': fvd_results, 'fvd_video_setting': videos1.shape,
+            'fvd_video_setting_name': 'batch_size, channel, time, heigth, width'}
+
+
+def calculate_fvd1(videos1, videos2, device, mini_bs=10, i3d=None):
+    """calculate_fvd.py:67-74."""
+    i3d = i3d if i3d is not None else load_i3d_pretrained(device=device)
+    feats1 = get_fvd_feats(trans(videos1), i3d=i3d, device=device, bs=mini_bs)
+    feats2 = get_fvd_feats(trans(videos2), i3d=i3d, device=device, bs=mini_bs)
+    return frechet_distance(feats1, feats2)
+
+
+def calculate_fvd2(feats1, feats2):
+    """calculate_fvd.py:76-77."""
+    return frechet_distance(feats1, feats2)

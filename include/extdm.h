@@ -38,6 +38,11 @@
  *                        loops of calculate_psnr2 / calculate_ssim2, valid.py:226-233)
  *                                                   metrics/calculate_psnr.py:6-15,
  *                                                   metrics/calculate_ssim.py:6-41
+ *   extdm_fvd_create / _load_weight / _finalize
+ *                        InceptionI3d.__init__ + load_state_dict      metrics/pytorch_i3d.py:172-303
+ *   extdm_fvd_features   InceptionI3d.forward / extract_features      metrics/pytorch_i3d.py:305-322
+ *   extdm_fvd_endpoint   the same forward cut after a VALID_ENDPOINTS name (parity hook)
+ *   extdm_fvd_preprocess trans + preprocess_single   metrics/calculate_fvd.py:6-14, fvd.py:161-187
  *
  * Limits: a denoiser sees tc + tp model frames (WO_REF: tc - 1 + tp); the temporal attention
  * holds one pixel's frames in at most 64 token slots, so extdm_finalize refuses more than 64
@@ -274,6 +279,61 @@ int extdm_frame_metrics(const float* a, const float* b, int N, int T, int C, int
 int extdm_bilinear_frames(float* dst, int B, int C, int T, int OH, int OW, const float* a, long a_sb, long a_sc,
                           long a_st, const float* b, long b_sb, long b_sc, long b_st, int t_split, int H, int W,
                           void* stream);
+
+/* ---- FVD features: InceptionI3d (metrics/pytorch_i3d.py:135-322) on a handle of its own ----
+ * The network shares nothing with an ExtdmHandle. Weights go in under the reference's state_dict
+ * keys (the public i3d_pretrained_400.pt layout: `Conv3d_1a_7x7.conv3d.weight`,
+ * `Mixed_3b.b1b.bn.running_var`, `logits.conv3d.bias`, ...; `num_batches_tracked` entries are
+ * accepted and ignored). extdm_fvd_finalize packs them for the f16x3 3-D convolution, folds every
+ * BatchNorm3d (eval, eps 1e-5) into a per-channel scale / shift and plans the workspace at
+ * max_batch x max_frames x 224 x 224; a missing key is an error naming the key. */
+typedef struct ExtdmFvdHandle ExtdmFvdHandle;
+int extdm_fvd_create(int num_classes, int in_channels, int max_batch, int max_frames, int device,
+                     ExtdmFvdHandle** out);
+void extdm_fvd_destroy(ExtdmFvdHandle* h);
+int extdm_fvd_load_weight(ExtdmFvdHandle* h, const char* name, const void* host_ptr, int dtype,
+                          const int64_t* shape, int ndim);
+int extdm_fvd_finalize(ExtdmFvdHandle* h);
+
+/* trans + preprocess_single (calculate_fvd.py:6-14, fvd.py:161-187) in one launch: in
+ * [B][T][C][H][W] in [0, 1] through element strides (planes contiguous H*W), C = 1 replicated to
+ * 3; temporal crop to sequence_length frames (0: none); bilinear resize (align_corners=False) of
+ * the shorter side to `resolution`, the longer to ceil(side * resolution / shorter); centre crop;
+ * (v - 0.5) * 2 -> out [B][3][T'][resolution][resolution]. Not tied to a handle. */
+int extdm_fvd_preprocess(const float* in, int B, int T, int C, int H, int W, long sb, long st, long sc,
+                         int sequence_length, int resolution, float* out, void* stream);
+
+/* InceptionI3d.forward / extract_features on x [N][in_channels][T][224][224]: logits_out
+ * [N][num_classes] (pre-softmax, the mean over the time slots) and / or pooled_out
+ * [N][1024][T'' - 1] (the AvgPool3d([2, 7, 7]) output), either may be NULL. T >= 9 (the
+ * reference's avg-pool raises below that) and N <= max_batch, T <= max_frames. A video's outputs
+ * do not depend on the batch it sits in. Fails if an f16x3 convolution input reached
+ * |v| >= 65504 (the sticky range flag, reset at entry). Synchronises the stream. */
+int extdm_fvd_features(ExtdmFvdHandle* h, int N, int T, const float* x, float* logits_out, float* pooled_out,
+                       void* stream);
+
+/* The parity hook: the network from x [N][in_channels][T][H][W] (any size the workspace holds) up
+ * to and including endpoint_name, one of VALID_ENDPOINTS `Conv3d_1a_7x7` ... `Mixed_5c`
+ * (pytorch_i3d.py:151-167), into out [N][C'][T'][H'][W']; extdm_fvd_endpoint_shape writes
+ * dims = {C', T', H', W'}. */
+int extdm_fvd_endpoint(ExtdmFvdHandle* h, int N, int T, int H, int W, const float* x, const char* endpoint_name,
+                       float* out, void* stream);
+int extdm_fvd_endpoint_shape(const ExtdmFvdHandle* h, int T, int H, int W, const char* endpoint_name, int* dims);
+
+/* MaxPool3dSamePadding.forward (pytorch_i3d.py:15-34) of a contiguous x [B][C][T][H][W] into a
+ * contiguous out [B][C][ceil(T/st)][ceil(H/sh)][ceil(W/sw)]: the 'same' rule's zero padding, then
+ * the max, so a padded 0 beats negative values. Windows [1,3,3], [3,3,3] and [2,2,2] (the
+ * network's), any stride. Not tied to a handle. */
+int extdm_fvd_maxpool(const float* x, int B, int C, int T, int H, int W, int kt, int kh, int kw, int st, int sh,
+                      int sw, float* out, void* stream);
+
+/* The host pad arithmetic of the launches above: the 'same' rule of Unit3D / MaxPool3dSamePadding
+ * (pytorch_i3d.py:9-13, 71-95) for one dimension. Returns the output extent ceil(size / stride)
+ * and writes the front and back zero pads (-1: bad argument). No device needed. */
+int extdm_fvd_same_pad(int size, int kernel, int stride, int* front, int* back);
+
+/* 1 if a convolution input of this handle reached |v| >= 65504 since the last reset. */
+int extdm_fvd_range_flag(ExtdmFvdHandle* h, int reset, void* stream);
 
 #ifdef __cplusplus
 }
