@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "host_util.h"
 #include "kernels.h"
 
 namespace extdm {
@@ -211,10 +212,10 @@ __global__ __launch_bounds__(256) void conv_gemm_kernel(ConvArgs a) {
   }
 }
 
-bool getenv_flag(const char* n) {
-  static int cached = -1;
-  if (cached < 0) { const char* v = getenv(n); cached = (v && v[0] && v[0] != '0') ? 1 : 0; }
-  return cached == 1;
+// EXTDM_NO_HALO=1, read once when a conv first reaches the halo route
+bool halo_off() {
+  static const bool off = env_flag("EXTDM_NO_HALO");
+  return off;
 }
 
 template <int KH, int KW, int MODE>
@@ -248,7 +249,7 @@ int conv_forward(hipStream_t s, const View& out, const View& in0, const View* in
   ConvEpi epi = epi_in;  // the other paths leave the statistics to the caller
   epi.stats = nullptr;
   if (conv_gemm_x3_forward(s, out, in0, in1, w, stride, pad, epi)) return 0;
-  if (w.mode == MODE_CONV && stride == 1 && w.KH == w.KW && pad == w.KH / 2 && !getenv_flag("EXTDM_NO_HALO") &&
+  if (w.mode == MODE_CONV && stride == 1 && w.KH == w.KW && pad == w.KH / 2 && !halo_off() &&
       conv_halo_forward(s, out, in0, in1, w, epi))
     return 0;
   ConvArgs a{};

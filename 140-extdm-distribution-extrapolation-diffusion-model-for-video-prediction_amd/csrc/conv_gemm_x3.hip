@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "host_util.h"
 #include "kernels.h"
 
 namespace extdm {
@@ -340,7 +341,7 @@ void launch_f(hipStream_t s, const GArgs& a, dim3 grid) {
 // the tap-major gather (TAPK above): a tap-major packing, whole 8-channel groups per source,
 // every pixel's byte offset (frame base included) below 2^32
 bool gemm_tapk_ok(const GArgs& a, int two) {
-  static const bool off = [] { const char* v = getenv("EXTDM_GEMM_NOTAPK"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_GEMM_NOTAPK");
   if (off || !a.wt || a.Cin % 8 != 0 || a.C0 % 8 != 0) return false;
   auto ext = [&](long sb, long sc, long st, int C) {
     return ((long)(a.B - 1) * sb + (long)(C - 1) * sc + (long)(a.T - 1) * st + (long)a.Hin * a.Win) * 4;
@@ -354,7 +355,7 @@ bool gemm_tapk_ok(const GArgs& a, int two) {
 
 // the fast gather (FAST above): taps that repeat per K tile, one source, 31-bit byte offsets
 bool gemm_fast_ok(const GArgs& a, int kk, int mode) {
-  static const bool off = [] { const char* v = getenv("EXTDM_GEMM_NOFAST"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_GEMM_NOFAST");
   if (off || BK % kk != 0 || mode == MODE_UP2 || a.Cin != a.C0) return false;
   const long bytes = ((long)(a.B - 1) * a.i0b + (long)(a.Cin - 1) * a.i0c + (long)(a.T - 1) * a.i0t +
                       (long)a.Hin * a.Win) * 4;

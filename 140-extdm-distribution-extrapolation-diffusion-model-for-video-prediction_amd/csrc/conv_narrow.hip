@@ -14,6 +14,7 @@
 #include <cstdlib>
 #include <stdexcept>
 
+#include "host_util.h"
 #include "kernels.h"
 
 namespace extdm {
@@ -193,7 +194,7 @@ void launch(hipStream_t s, const NArgs& a, dim3 grid) {
 }  // namespace
 
 bool narrow_off() {
-  static const bool off = [] { const char* v = getenv("EXTDM_NO_NARROW"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_NO_NARROW");
   return off;
 }
 

@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "host_util.h"
 #include "kernels.h"
 
 // EXTDM_X3_LIN: the staged (fp32-input) X tile of the one-group tiles in the operand layout
@@ -872,7 +873,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
 
 // the BX precondition: the kernel's bufx test (whole 16-channel groups in each source, extents set)
 bool x3_bufx_ok(const X3Args& a, int cib) {
-  static const bool off = [] { const char* v = getenv("EXTDM_X3_NO_BX"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_X3_NO_BX");
   return !off && EXTDM_X3_BUFX && a.C0 % 16 == 0 && a.Cin % cib == 0 && a.in0_bytes > 0;
 }
 
@@ -962,7 +963,7 @@ int split_slices_longk(const X3Args& a) {
 }
 
 int split_slices(const X3Args& a, unsigned ntiles, long max_wg, long max_total, int bm = 128) {
-  static const bool off = [] { const char* v = getenv("EXTDM_NO_SPLITK"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_NO_SPLITK");
   (void)ntiles;
   if (off || a.ncgb < 4 || a.P < 1) return 0;
   if (bm == 256 && a.ncgb >= kLongKBlocks) return split_slices_longk(a);
@@ -1036,7 +1037,7 @@ void x3_split128(bool four, long& max_wg, long& max_total) {
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF>
 void launch(hipStream_t s, const X3Args& a, unsigned ntiles) {
   // EXTDM_X3_NOSPAN=1: per-stage __syncthreads() (A/B against the spanning barriers)
-  static const bool nospan = [] { const char* v = getenv("EXTDM_X3_NOSPAN"); return v && v[0] && v[0] != '0'; }();
+  static const bool nospan = env_flag("EXTDM_X3_NOSPAN");
   if (nospan) launch_ns<KS, KY, BM, BN, NG, WN, NW, XBUF, false>(s, a, ntiles);
   else launch_ns<KS, KY, BM, BN, NG, WN, NW, XBUF, true>(s, a, ntiles);
 }
@@ -1151,7 +1152,7 @@ bool x3_setup(const View& out, const View& in0, const View* in1, const PackedW& 
 // lo) fits comfortably in one XCD's 4 MiB L2 and there is more than one m-tile.
 // EXTDM_X3_NO_MFAST=1 turns it off (A/B).
 bool x3_mfast(const X3Args& a, const X3Tile& tl, unsigned ntiles) {
-  static const bool off = [] { const char* v = getenv("EXTDM_X3_NO_MFAST"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_X3_NO_MFAST");
   static const long cap = [] { const char* v = getenv("EXTDM_X3_MFAST_KB"); return (v ? atol(v) : 3584L) * 1024; }();
   const long mt = (a.Cout + tl.bm - 1) / tl.bm;
   return !off && mt > 1 && ntiles % 8 == 0 && mt * tl.bm * (long)a.Cin * 4 <= cap;
@@ -1352,10 +1353,7 @@ size_t x3op_halves(int B, int C, int T, int H, int W, int pad) {
 bool conv_x3_op_supported(const View& out, const PackedW& w, int C, int pad) {
   if (!w.wx || w.mode != MODE_CONV || w.KH != 3 || w.KW != 3 || pad != 1 || w.xng != 1 || C % 16 != 0) return false;
   // EXTDM_NO_X3OP=1: the producer writes fp32 and the conv stages it (A/B)
-  static const bool off = [] {
-    auto on = [](const char* n) { const char* v = getenv(n); return v && v[0] && v[0] != '0'; };
-    return on("EXTDM_X3_NOSPAN") || on("EXTDM_NO_X3OP");
-  }();
+  static const bool off = env_flag("EXTDM_X3_NOSPAN") || env_flag("EXTDM_NO_X3OP");
   if (off) return false;
   const int H = out.H, W = out.W, bn = w.xbn;
   if (W > bn || bn % W != 0) return false;

@@ -1,6 +1,6 @@
 // The FVD feature network's runtime: an InceptionI3d (metrics/pytorch_i3d.py:135-322) handle of
-// its own -- weight registry under the reference's state_dict keys, f16x3 packing with the
-// BatchNorm3d folded into a per-channel scale / shift, a workspace planned at
+// its own -- weight registry under the reference's state_dict keys, the f16x3 layout and the
+// BatchNorm3d fold of pack.cpp uploaded per unit, a workspace planned at
 // max_batch x max_frames x 224^2, the forward as a sequence of i3d.hip launches -- and the
 // extdm_fvd_* part of the C ABI (include/extdm.h).
 #include <hip/hip_runtime.h>
@@ -15,27 +15,13 @@
 #include <vector>
 
 #include "extdm.h"
+#include "host_util.h"
 #include "i3d.h"
+#include "pack.h"
 
 using namespace extdm;
 
 namespace {
-
-struct Error : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess)                                                                  \
-      throw Error(std::string(#x) + " failed: " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
-  } while (0)
-
-#define REQUIRE(c, msg) \
-  do {                  \
-    if (!(c)) throw Error(msg); \
-  } while (0)
 
 struct HostW {
   std::vector<float> f;
@@ -63,17 +49,6 @@ struct Unit {
 };
 
 enum Slot { SX0 = 0, SX1 = 1, ST1 = 2, ST2 = 3, ST3 = 4, SPOOL = 5, NSLOT = 6 };
-
-template <class F>
-int guarded(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    set_last_error(e.what());
-    return -1;
-  }
-}
 
 }  // namespace
 
@@ -121,65 +96,21 @@ struct ExtdmFvdHandle {
   }
 
   // Unit3D (pytorch_i3d.py:37-103) `name`: conv3d.weight [M][Cin][KS]^3 packed for conv3d_x3_kernel
-  // ([mtile][ktile][step][m32][hi|lo][lane][8], row m = mtile * BM + m32 * 32 + (lane & 31),
-  // k = ktile * 32 + step * 16 + 8 * (lane >> 5) + e = tap * Cpad + ci; row m scaled by 2^s(m) so
-  // that max |w| lies in [2^14, 2^15), undone by wscale[m]), bn.* folded into scale / shift.
+  // (pack_unit3d; the 3-channel stem in its (kt, ky)-row layout, i3d.hip STEM), bn.* folded into
+  // scale / shift (BatchNorm3d eval, pytorch_i3d.py:69).
   void pack_unit(const std::string& name, int M, int Cin, int KS) {
     const HostW& wt = H(name + ".conv3d.weight", {M, Cin, KS, KS, KS});
-    // the 3-channel stem packs (kt, ky) rows of 7 kx * 3 ci = 21 elements padded to 24 (i3d.hip STEM)
     const bool stem = KS == 7 && Cin == 3 && M == 64;
-    const int KK = KS * KS * KS, Cpad = (Cin + 7) / 8 * 8, K = stem ? 49 * kStemRow : KK * Cpad;
-    const int bm = conv3d_bm(M), nkt = (K + 31) / 32, mt = (M + bm - 1) / bm, m32 = bm / 32;
-    const size_t ah = (size_t)2 * m32 * 2 * 512;
-    std::vector<float> scale(M), rs(M);
-    for (int m = 0; m < M; ++m) {
-      float mx = 0.f;
-      for (size_t k = 0; k < (size_t)Cin * KK; ++k) mx = std::max(mx, std::fabs(wt.f[(size_t)m * Cin * KK + k]));
-      int e = 0;
-      if (mx > 0.f) { std::frexp(mx, &e); e = 15 - e; }
-      scale[m] = std::ldexp(1.f, e);
-      rs[m] = std::ldexp(1.f, -e);
-    }
-    std::vector<_Float16> g((size_t)mt * nkt * ah, (_Float16)0.f);
-    for (int mtile = 0; mtile < mt; ++mtile)
-      for (int kt = 0; kt < nkt; ++kt)
-        for (int st = 0; st < 2; ++st)
-          for (int q = 0; q < m32; ++q)
-            for (int l = 0; l < 64; ++l)
-              for (int e = 0; e < 8; ++e) {
-                const int m = mtile * bm + q * 32 + (l & 31), k = kt * 32 + st * 16 + 8 * (l >> 5) + e;
-                if (m >= M || k >= K) continue;
-                int tap = k / Cpad, ci = k - tap * Cpad;
-                if (stem) {
-                  const int row = k / kStemRow, j = k - row * kStemRow;
-                  if (j >= 21) continue;
-                  tap = row * 7 + j / 3;
-                  ci = j % 3;
-                }
-                if (ci >= Cin) continue;
-                const float v = wt.f[((size_t)m * Cin + ci) * KK + tap] * scale[m];
-                const _Float16 hi = (_Float16)v;
-                const size_t base = ((size_t)mtile * nkt + kt) * ah + (size_t)((st * m32 + q) * 2) * 512;
-                g[base + l * 8 + e] = hi;
-                g[base + 512 + l * 8 + e] = (_Float16)(v - (float)hi);
-              }
+    const int bm = conv3d_bm(M), Cpad = (Cin + 7) / 8 * 8;
+    const Frags p = pack_unit3d(wt.f, M, Cin, Cpad, KS, bm, stem ? kStemRow : 0);
     Unit u;
-    u.w.w = upload(g);
-    u.w.wscale = upload(rs);
-    u.w.M = M; u.w.Cin = Cin; u.w.Cpad = Cpad; u.w.KS = KS; u.w.bm = bm; u.w.nkt = nkt; u.w.stem = stem;
-    // BatchNorm3d (eval, eps 1e-5; pytorch_i3d.py:69): y = x * sc + sh, computed in fp64
-    const HostW& bw = H(name + ".bn.weight", {M});
-    const HostW& bb = H(name + ".bn.bias", {M});
-    const HostW& bmn = H(name + ".bn.running_mean", {M});
-    const HostW& bv = H(name + ".bn.running_var", {M});
-    std::vector<float> sc(M), sh(M);
-    for (int m = 0; m < M; ++m) {
-      const double s_ = (double)bw.f[m] / std::sqrt((double)bv.f[m] + 1e-5);
-      sc[m] = (float)s_;
-      sh[m] = (float)((double)bb.f[m] - (double)bmn.f[m] * s_);
-    }
-    u.scale = upload(sc);
-    u.shift = upload(sh);
+    u.w.w = upload(p.g);
+    u.w.wscale = upload(p.rs);
+    u.w.M = M; u.w.Cin = Cin; u.w.Cpad = Cpad; u.w.KS = KS; u.w.bm = bm; u.w.nkt = p.n; u.w.stem = stem;
+    const Affine bn = bn_fold_f64(H(name + ".bn.weight", {M}).f, H(name + ".bn.bias", {M}).f,
+                                  H(name + ".bn.running_mean", {M}).f, H(name + ".bn.running_var", {M}).f);
+    u.scale = upload(bn.a);
+    u.shift = upload(bn.b);
     units[name] = u;
   }
 

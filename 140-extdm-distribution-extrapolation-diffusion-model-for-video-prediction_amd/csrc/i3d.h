@@ -1,5 +1,4 @@
-// InceptionI3d (the FVD feature network, metrics/pytorch_i3d.py) -- kernels of i3d.hip and the
-// pieces fvd.cpp shares with runtime.cpp.
+// InceptionI3d (the FVD feature network, metrics/pytorch_i3d.py) -- kernels of i3d.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -59,8 +58,5 @@ void i3d_logits(hipStream_t s, const float* pooled, const float* wt, const float
 // to R (resized extents Hr x Wr), centre crop at (y0, x0), (v - 0.5) * 2
 void fvd_preprocess(hipStream_t s, const float* in, long sb, long st, long sc, int B, int C, int To, int H, int W,
                     int Hr, int Wr, int y0, int x0, int R, float* out);
-
-// the thread's extdm_last_error message (runtime.cpp)
-void set_last_error(const std::string& msg);
 
 }  // namespace extdm

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "host_util.h"
 #include "kernels.h"
 
 // EXTDM_PW_EXP (diagnostic builds only, results invalid): bit 0 = output stores predicated off,
@@ -290,8 +291,7 @@ int view_bytes(const View& v) {
 
 // read per launch decision (not cached): tests compare both paths in one process
 bool pw_x3_enabled() {
-  const char* v = getenv("EXTDM_NO_PW");
-  return !(v && v[0] && v[0] != '0');
+  return !env_flag("EXTDM_NO_PW");
 }
 
 bool pw_x3_forward(hipStream_t s, const View& out, const View& in, const PackedW& w, const ConvEpi& e) {

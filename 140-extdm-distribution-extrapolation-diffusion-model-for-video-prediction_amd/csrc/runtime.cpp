@@ -1,7 +1,7 @@
-// ExtDM sampling runtime: weight registry and packing, t-only tables, the
-// u12 Unet3D forward as a sequence of HIP kernel launches over a stack-arena
-// workspace, the sampler loop replayed from one captured hipGraph step, and
-// the C ABI of include/extdm.h.
+// ExtDM sampling runtime: weight registry (the layouts are computed by pack.cpp; the handle
+// uploads and caches them), t-only tables, the u12 Unet3D forward as a sequence of HIP kernel
+// launches over a stack-arena workspace, the sampler loop replayed from one captured hipGraph
+// step, and the C ABI of include/extdm.h.
 //
 // Forward structure follows Unet3D.forward (DenoiseNet_..._u12.py:1017-1086);
 // each helper cites the reference block it implements.
@@ -20,7 +20,9 @@
 #include <vector>
 
 #include "extdm.h"
+#include "host_util.h"
 #include "kernels.h"
+#include "pack.h"
 
 using namespace extdm;
 
@@ -30,22 +32,6 @@ static constexpr int kTrajHeads = 8;
 namespace {
 
 thread_local std::string g_last_error;
-
-struct Error : std::runtime_error {
-  using std::runtime_error::runtime_error;
-};
-
-#define HIPCHK(x)                                                                          \
-  do {                                                                                     \
-    hipError_t e_ = (x);                                                                   \
-    if (e_ != hipSuccess)                                                                  \
-      throw Error(std::string(#x) + " failed: " + hipGetErrorString(e_) + " @" + std::to_string(__LINE__)); \
-  } while (0)
-
-#define REQUIRE(c, msg) \
-  do {                  \
-    if (!(c)) throw Error(msg); \
-  } while (0)
 
 struct HostTensor {
   std::vector<float> f;
@@ -113,9 +99,9 @@ struct ExtdmHandle {
   Arena arena;
   double* partials = nullptr;
   // EXTDM_NO_GN_FUSE=1: separate GroupNorm statistics pass after every ResnetBlock conv
-  const bool fuse_gn_stats = [] { const char* v = getenv("EXTDM_NO_GN_FUSE"); return !(v && v[0] && v[0] != '0'); }();
+  const bool fuse_gn_stats = !env_flag("EXTDM_NO_GN_FUSE");
   // EXTDM_NO_RES_GN=1: block2's GroupNorm applied in place before res_conv (A/B)
-  const bool fuse_res_gn = [] { const char* v = getenv("EXTDM_NO_RES_GN"); return !(v && v[0] && v[0] != '0'); }();
+  const bool fuse_res_gn = !env_flag("EXTDM_NO_RES_GN");
   int* t_batch = nullptr;
   int* step_ctr = nullptr;
   unsigned* sel = nullptr;  // the multi-workgroup sampler step's selection workspace (sampler_sel_bytes)
@@ -124,7 +110,7 @@ struct ExtdmHandle {
   // the sampler step over (chunk, sample) workgroups (sampler.hip); EXTDM_SAMPLER_1WG=1 restores the
   // one-workgroup-per-sample kernel with its set_t / incr launches (A/B)
   static bool sampler_mw() {
-    static const bool off = [] { const char* v = getenv("EXTDM_SAMPLER_1WG"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_SAMPLER_1WG");
     return !off;
   }
   StepCoef* coefs = nullptr;
@@ -149,6 +135,12 @@ struct ExtdmHandle {
     allocations.push_back(p);
     return reinterpret_cast<float*>(p);
   }
+  template <class T>
+  T* upload(const std::vector<T>& v) {
+    T* d = reinterpret_cast<T*>(dmalloc(v.size() * sizeof(T)));
+    HIPCHK(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
   const HostTensor& H(const std::string& n) const {
     auto it = host.find(n);
     if (it == host.end()) throw Error("missing weight: " + n);
@@ -160,402 +152,137 @@ struct ExtdmHandle {
     if (it != dev.end()) return it->second;
     const HostTensor& t = H(n);
     REQUIRE(!t.is_int, "expected float tensor: " + n);
-    float* p = dmalloc(t.f.size() * sizeof(float));
-    HIPCHK(hipMemcpy(p, t.f.data(), t.f.size() * sizeof(float), hipMemcpyHostToDevice));
-    dev[n] = p;
-    return p;
+    return dev[n] = upload(t.f);
   }
 
-  // Pack a conv weight W[co][ci][(kt)][kh][kw] (or linear W[co][ci]) as
-  // A[k][m], k = ci*kh*kw + ky*kw + kx, zero padded.
+  // Weight packing: pack.h defines every layout; the methods below look up the cache, fetch
+  // H(name), call the pack function with the kernels' tile parameters, and upload.
+  // A conv weight W[co][ci][(kt)][kh][kw] (or linear W[co][ci]) in every layout its routes read
   const PackedW& P(const std::string& n) {
     auto it = packed.find(n);
     if (it != packed.end()) return it->second;
     const HostTensor& t = H(n);
     const auto& sh = t.shape;
-    PackedW pw;
-    int co = (int)sh[0], ci = (int)sh[1];
+    const int co = (int)sh[0], ci = (int)sh[1], bm = conv_bm(co);
     int kh = 1, kw = 1;
     if (sh.size() >= 4) { kh = (int)sh[sh.size() - 2]; kw = (int)sh[sh.size() - 1]; }
-    pw.M = co; pw.K = ci * kh * kw; pw.KH = kh; pw.KW = kw;
-    const int bm = conv_bm(co);
-    pw.Mpad = (co + bm - 1) / bm * bm;
-    pw.Kpad = (pw.K + 15) / 16 * 16;
-    std::vector<float> a((size_t)pw.Kpad * pw.Mpad, 0.f);
-    for (int m = 0; m < co; ++m)
-      for (int k = 0; k < pw.K; ++k) a[(size_t)k * pw.Mpad + m] = t.f[(size_t)m * pw.K + k];
-    pw.w = dmalloc(a.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.w, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (kh == kw && (kh == 1 || kh == 3 || kh == 7) && co > 32) pack_halo(pw, t.f, ci);
-    if (x3_convs() && kh == kw && (kh == 1 || kh == 3 || kh == 5 || kh == 7) && co > 32 &&
-        ci >= 16)
-      pack_x3(pw, t.f, ci);
-    if (x3_convs()) pack_gemm_x3(pw, a, 1);
-    if (kh == kw && narrow_cot(kh, co) > 0) pack_narrow(pw, t.f, ci);
+    const GemmPlane a = pack_gemm_plane(t.f, co, ci * kh * kw, bm);
+    PackedW pw = gemm_weight(a, co, ci * kh * kw);
+    pw.KH = kh; pw.KW = kw;
+    if (kh == kw && (kh == 1 || kh == 3 || kh == 7) && co > 32) {
+      const HaloPack h = pack_halo(t.f, kh, co, ci, bm, halo_ch(kh, bm));
+      pw.wh = upload(h.a);
+      pw.hstages = h.stages; pw.hbm = bm;
+    }
+    if (x3_convs() && kh == kw && (kh == 1 || kh == 3 || kh == 5 || kh == 7) && co > 32 && ci >= 16) {
+      const X3Tile tl = x3_tile(kh, co);
+      const Frags x = pack_x3(t.f, kh, co, ci, tl.bm, tl.ng);
+      pw.wx = upload(x.g);
+      pw.xscale = upload(x.rs);
+      pw.xbm = tl.bm; pw.xbn = tl.bn; pw.xng = tl.ng; pw.xncgb = x.n;
+    }
+    if (x3_convs()) upload_gemm_x3(pw, a, 1);
+    if (kh == kw && narrow_cot(kh, co) > 0) {
+      pw.vcot = narrow_cot(kh, co);
+      pw.wv = upload(pack_narrow(t.f, kh * kw, co, ci, pw.vcot));
+    }
     return packed[n] = pw;
   }
-  // fp32 direct VALU layout (conv_narrow.hip): [group][ci][tap][vcot rounded up to 4], m =
-  // group * vcot + o
-  void pack_narrow(PackedW& pw, const std::vector<float>& w, int ci) {
-    const int kk = pw.KH * pw.KW, co = pw.M, cot = narrow_cot(pw.KH, co), ng = (co + cot - 1) / cot;
-    const int cotp = (cot + 3) & ~3;
-    std::vector<float> a((size_t)ng * ci * kk * cotp, 0.f);
-    for (int m = 0; m < co; ++m)
-      for (int c = 0; c < ci; ++c)
-        for (int tap = 0; tap < kk; ++tap)
-          a[(((size_t)(m / cot) * ci + c) * kk + tap) * cotp + m % cot] = w[((size_t)m * ci + c) * kk + tap];
-    pw.wv = dmalloc(a.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.wv, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-    pw.vcot = cot;
+  PackedW gemm_weight(const GemmPlane& a, int M, int K) {
+    PackedW pw;
+    pw.M = M; pw.K = K; pw.Mpad = a.Mpad; pw.Kpad = a.Kpad;
+    pw.w = upload(a.a);
+    return pw;
   }
-  // f16x3 implicit-GEMM layout (conv_gemm_x3.hip) from the fp32 GEMM packing a
-  // [npar][Kpad][Mpad]: [par][mtile][ktile][step][m32][hi|lo][lane][8], row m = mtile*BM +
-  // m32*32 + (lane & 31), k = ktile*32 + step*16 + 8*(lane >> 5) + e. Row m is scaled by
-  // 2^s(m) over all parities (max |w| -> [2^14, 2^15)), undone by gscale[m] = 2^-s(m).
-  void pack_gemm_x3(PackedW& pw, const std::vector<float>& a, int npar) {
-    const int M = pw.M, K = pw.K, bm = conv_bm(M);
-    const int nkt = (K + 31) / 32, mt = (M + bm - 1) / bm, m32 = bm / 32;
-    const size_t ah = (size_t)2 * m32 * 2 * 512, plane = (size_t)pw.Kpad * pw.Mpad;
-    std::vector<float> scale(M), rs(M);
-    for (int m = 0; m < M; ++m) {
-      float mx = 0.f;
-      for (int par = 0; par < npar; ++par)
-        for (int k = 0; k < K; ++k) mx = std::max(mx, std::fabs(a[par * plane + (size_t)k * pw.Mpad + m]));
-      int e = 0;
-      if (mx > 0.f) { std::frexp(mx, &e); e = 15 - e; }
-      scale[m] = std::ldexp(1.f, e);
-      rs[m] = std::ldexp(1.f, -e);
-    }
-    // kmap(k): the row of `a` GEMM row k of this packing reads (identity: ci-major; the
-    // tap-major copy below: k = tap * ci + c -> c * KK + tap)
-    auto pack = [&](auto kmap) {
-      std::vector<_Float16> g((size_t)npar * mt * nkt * ah, (_Float16)0.f);
-      for (int par = 0; par < npar; ++par)
-        for (int mtile = 0; mtile < mt; ++mtile)
-          for (int kt = 0; kt < nkt; ++kt)
-            for (int st = 0; st < 2; ++st)
-              for (int q = 0; q < m32; ++q)
-                for (int l = 0; l < 64; ++l)
-                  for (int e = 0; e < 8; ++e) {
-                    const int m = mtile * bm + q * 32 + (l & 31), k = kt * 32 + st * 16 + 8 * (l >> 5) + e;
-                    if (m >= M || k >= K) continue;
-                    const float v = a[par * plane + (size_t)kmap(k) * pw.Mpad + m] * scale[m];
-                    const _Float16 hi = (_Float16)v;
-                    const size_t base = (((size_t)par * mt + mtile) * nkt + kt) * ah + (size_t)((st * m32 + q) * 2) * 512;
-                    g[base + l * 8 + e] = hi;
-                    g[base + 512 + l * 8 + e] = (_Float16)(v - (float)hi);
-                  }
-      void* d = dmalloc(g.size() * sizeof(_Float16));
-      HIPCHK(hipMemcpy(d, g.data(), g.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-      return d;
-    };
-    pw.gx = pack([](int k) { return k; });
-    pw.gscale = dmalloc(M * sizeof(float));
-    HIPCHK(hipMemcpy(pw.gscale, rs.data(), M * sizeof(float), hipMemcpyHostToDevice));
-    pw.gbm = bm; pw.gnkt = nkt;
-    const int kk = pw.KH * pw.KW, ci = K / kk;
-    if (npar == 1 && kk > 1 && 32 % kk != 0 && ci % 8 == 0) {
-      pw.gxt = pack([&](int k) { const int tap = k / ci, c = k - tap * ci; return c * kk + tap; });
-      pw.gnkt_t = nkt;
-    }
+  // the f16x3 implicit-GEMM fragments (conv_gemm_x3.hip) of the fp32 planes a
+  void upload_gemm_x3(PackedW& pw, const GemmPlane& a, int npar) {
+    const int bm = conv_bm(pw.M);
+    const Frags g = pack_gemm_x3(a, npar, pw.M, pw.K, bm, pw.KH * pw.KW);
+    pw.gx = upload(g.g);
+    pw.gscale = upload(g.rs);
+    pw.gbm = bm; pw.gnkt = g.n;
+    if (!g.tap_major.empty()) { pw.gxt = upload(g.tap_major); pw.gnkt_t = g.n; }
   }
-  // f16x3 layout (conv_x3.hip): [mtile][cb*KS + ky][(g, kx)][m32][hi|lo][lane][8], lane =
-  // (h, lc): row m = mtile*BM + m32*32 + lc, input channel cb*16NG + g*16 + 8h + e. Row m is
-  // scaled by 2^s(m) (max |w| -> [2^14, 2^15)), undone by xscale[m] = 2^-s(m) in the epilogue.
-  void pack_x3(PackedW& pw, const std::vector<float>& w, int ci) {
-    const int ks = pw.KH, kk = ks * ks, co = pw.M;
-    const X3Tile tl = x3_tile(ks, co);
-    const int cib = 16 * tl.ng, ncgb = (ci + cib - 1) / cib, mt = (co + tl.bm - 1) / tl.bm;
-    const int m32 = tl.bm / 32, steps = tl.ng * ks;
-    const size_t ah = (size_t)steps * m32 * 2 * 512;
-    std::vector<float> scale(co), rs(co);
-    for (int m = 0; m < co; ++m) {
-      float mx = 0.f;
-      for (size_t k = 0; k < (size_t)ci * kk; ++k) mx = std::max(mx, std::fabs(w[(size_t)m * ci * kk + k]));
-      int e = 0;
-      if (mx > 0.f) { std::frexp(mx, &e); e = 15 - e; }  // mx * 2^e in [2^14, 2^15)
-      scale[m] = std::ldexp(1.f, e);
-      rs[m] = std::ldexp(1.f, -e);
-    }
-    std::vector<_Float16> a((size_t)mt * ncgb * ks * ah, (_Float16)0.f);
-    for (int mtile = 0; mtile < mt; ++mtile)
-      for (int cb = 0; cb < ncgb; ++cb)
-        for (int ky = 0; ky < ks; ++ky)
-          for (int g = 0; g < tl.ng; ++g)
-            for (int kx = 0; kx < ks; ++kx)
-              for (int q = 0; q < m32; ++q)
-                for (int l = 0; l < 64; ++l)
-                  for (int e = 0; e < 8; ++e) {
-                    const int m = mtile * tl.bm + q * 32 + (l & 31);
-                    const int c = cb * cib + g * 16 + 8 * (l >> 5) + e;
-                    if (m >= co || c >= ci) continue;
-                    const float v = w[((size_t)m * ci + c) * kk + ky * ks + kx] * scale[m];
-                    const _Float16 hi = (_Float16)v;
-                    const _Float16 lo = (_Float16)(v - (float)hi);
-                    const size_t base = (((((size_t)mtile * ncgb + cb) * ks + ky) * steps + g * ks + kx) * m32 + q) * 2;
-                    a[(base + 0) * 512 + l * 8 + e] = hi;
-                    a[(base + 1) * 512 + l * 8 + e] = lo;
-                  }
-    pw.wx = dmalloc(a.size() * sizeof(_Float16));
-    HIPCHK(hipMemcpy(pw.wx, a.data(), a.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    pw.xscale = dmalloc(co * sizeof(float));
-    HIPCHK(hipMemcpy(pw.xscale, rs.data(), co * sizeof(float), hipMemcpyHostToDevice));
-    pw.xbm = tl.bm; pw.xbn = tl.bn; pw.xng = tl.ng; pw.xncgb = ncgb;
-  }
-  // Direct-conv layout [mtile][stage][step][half][BM]: step = (cp*k + ky)*k + kx,
-  // input channel = stage*2CH + half*CH + cp (conv_halo.hip).
-  void pack_halo(PackedW& pw, const std::vector<float>& w, int ci) {
-    const int ks = pw.KH, kk = ks * ks, co = pw.M;
-    const int bm = conv_bm(co);
-    const int ch = halo_ch(ks, bm), cib = 2 * ch;
-    const int stages = (ci + cib - 1) / cib;
-    const int mt = (co + bm - 1) / bm;
-    const size_t afl = (size_t)ch * kk * 2 * bm;
-    std::vector<float> a((size_t)mt * stages * afl, 0.f);
-    for (int m = 0; m < co; ++m) {
-      const int mtile = m / bm, mm = m % bm;
-      for (int c = 0; c < ci; ++c) {
-        const int st = c / cib, rem = c % cib, half = rem / ch, cp = rem % ch;
-        for (int tap = 0; tap < kk; ++tap) {
-          const int step = cp * kk + tap;
-          a[((size_t)mtile * stages + st) * afl + ((size_t)step * 2 + half) * bm + mm] =
-              w[((size_t)m * ci + c) * kk + tap];
-        }
-      }
-    }
-    pw.wh = dmalloc(a.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.wh, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-    pw.hstages = stages;
-    pw.hbm = bm;
-  }
-  // Conv3d weight W[co][ci][3][kh][kw] as a (1,kh,kw) conv over 3*ci channels
-  // ordered (kt, ci): W'[co][kt*ci + c] = W[co][c][kt].
+  // Conv3d weight W[co][ci][3][kh][kw] as a (1,kh,kw) conv over 3*ci channels (reorder_time3)
   const PackedW& Ptime3(const std::string& n) {
     const std::string key = n + "#t3";
     if (!host.count(key)) {
       const HostTensor& t = H(n);
       const int co = (int)t.shape[0], ci = (int)t.shape[1], kt = (int)t.shape[2];
-      const int kk = (int)(t.shape[3] * t.shape[4]);
-      HostTensor r;
-      r.shape = {co, (int64_t)kt * ci, t.shape[3], t.shape[4]};
-      r.f.resize(t.f.size());
-      for (int m = 0; m < co; ++m)
-        for (int c = 0; c < ci; ++c)
-          for (int z = 0; z < kt; ++z)
-            for (int q = 0; q < kk; ++q)
-              r.f[(((size_t)m * kt * ci) + (size_t)z * ci + c) * kk + q] = t.f[(((size_t)m * ci + c) * kt + z) * kk + q];
-      host[key] = std::move(r);
+      host[key] = HostTensor{reorder_time3(t.f, co, ci, kt, (int)(t.shape[3] * t.shape[4])), {},
+                             {co, (int64_t)kt * ci, t.shape[3], t.shape[4]}};
     }
     return P(key);
   }
-  // ConvTranspose3d(1,4,4)/s2/p1 weight W[ci][co][1][4][4] -> four 2x2 parity GEMMs:
-  // parity (py,px) tap (ky',kx') uses W[..][3-py-2ky'][3-px-2kx'].
+  // ConvTranspose3d(1,4,4)/s2/p1 weight W[ci][co][1][4][4] -> four 2x2 parity GEMMs
   const PackedW& Pdeconv(const std::string& n) {
     auto it = packed.find(n);
     if (it != packed.end()) return it->second;
     const HostTensor& t = H(n);
     const int ci = (int)t.shape[0], co = (int)t.shape[1];
     REQUIRE(t.shape[3] == 4 && t.shape[4] == 4, "deconv expects (1,4,4) kernels: " + n);
-    PackedW pw;
-    pw.M = co; pw.K = ci * 4; pw.KH = 2; pw.KW = 2; pw.mode = MODE_DECONV;
-    const int bm = conv_bm(co);
-    pw.Mpad = (co + bm - 1) / bm * bm;
-    pw.Kpad = (pw.K + 15) / 16 * 16;
-    const size_t plane = (size_t)pw.Kpad * pw.Mpad;
-    std::vector<float> a(4 * plane, 0.f);
-    for (int par = 0; par < 4; ++par) {
-      const int py = par >> 1, px = par & 1;
-      for (int c = 0; c < ci; ++c)
-        for (int ky = 0; ky < 2; ++ky)
-          for (int kx = 0; kx < 2; ++kx) {
-            const int k = c * 4 + ky * 2 + kx;
-            const int sy = 3 - py - 2 * ky, sx = 3 - px - 2 * kx;
-            for (int m = 0; m < co; ++m)
-              a[par * plane + (size_t)k * pw.Mpad + m] = t.f[(((size_t)c * co + m) * 4 + sy) * 4 + sx];
-          }
-    }
-    pw.w = dmalloc(a.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.w, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-    if (x3_convs()) pack_gemm_x3(pw, a, 4);
+    const GemmPlane a = pack_deconv_planes(t.f, ci, co, conv_bm(co));
+    PackedW pw = gemm_weight(a, co, ci * 4);
+    pw.KH = 2; pw.KW = 2; pw.mode = MODE_DECONV;
+    if (x3_convs()) upload_gemm_x3(pw, a, 4);
     return packed[n] = pw;
   }
-  PackedW pack_matrix(const std::vector<float>& wrow /*[M][K]*/, int M, int K) {
-    PackedW pw;
-    pw.M = M; pw.K = K;
-    const int bm = conv_bm(M);
-    pw.Mpad = (M + bm - 1) / bm * bm;
-    pw.Kpad = (K + 15) / 16 * 16;
-    std::vector<float> a((size_t)pw.Kpad * pw.Mpad, 0.f);
-    for (int m = 0; m < M; ++m)
-      for (int k = 0; k < K; ++k) a[(size_t)k * pw.Mpad + m] = wrow[(size_t)m * K + k];
-    pw.w = dmalloc(a.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.w, a.data(), a.size() * sizeof(float), hipMemcpyHostToDevice));
-    return pw;
-  }
 
-  // init_conv's x-branch composed with init_noise_conv (xpath_x3.hip): 49 border-class
-  // 13x13 kernels over the 3 latent channels, built in fp64, packed as f16x3 A fragments
-  // [class][kstep = (ci, dy)][m32][hi|lo][lane][8] (row m = m32*32 + (lane & 31), column
-  // dx = 8*(lane >> 5) + e, zero for dx >= 13), rows scaled by 2^s(class, m).
+  // init_conv's x-branch composed with init_noise_conv (xpath_x3.hip, pack_xpath)
   struct XPathW { void* w = nullptr; float* rs = nullptr; float* cb = nullptr; };
   XPathW xpw;
-  bool xpath_ready = false;
   bool xpath_enabled() const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_XPATH"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_XPATH");
     return !off && x3_convs() &&
            (cfg.arch == EXTDM_ARCH_U12 || cfg.arch == EXTDM_ARCH_ADA) && cfg.latent >= 7 && cfg.dim <= 64;
   }
   const XPathW& Pxpath() {
-    if (xpath_ready) return xpw;
+    if (xpw.w) return xpw;
     const HostTensor& wn = H("init_noise_conv.weight");  // [Cm][3][1][7][7]
-    const HostTensor& bnt = H("init_noise_conv.bias");
     const HostTensor& wi = H("init_conv.weight");        // [Co][Cm + Cf][1][7][7]
-    const HostTensor& bit = H("init_conv.bias");
     const int Cm = (int)wn.shape[0], Ci = (int)wn.shape[1], Co = (int)wi.shape[0], Cin = (int)wi.shape[1];
     REQUIRE(Ci == 3 && wn.shape.back() == 7 && wi.shape.back() == 7 && Cin > Cm && Co <= 64,
             "composed init_conv: unexpected init_noise_conv / init_conv shapes");
-    const int L = cfg.latent, M32 = (Co + 31) / 32, MP = M32 * 32;
-    // V[m][ci][a][b][e][f] = sum_c' Wa[m][c'][a][b] Wn[c'][ci][e][f]; U[m][a][b] = sum_c' Wa bn
-    std::vector<double> V((size_t)Co * 3 * 49 * 49, 0.0), U((size_t)Co * 49, 0.0);
-    for (int m = 0; m < Co; ++m)
-      for (int ab = 0; ab < 49; ++ab)
-        for (int c = 0; c < Cm; ++c) {
-          const double wa = wi.f[((size_t)m * Cin + c) * 49 + ab];
-          if (wa == 0.0) continue;
-          U[(size_t)m * 49 + ab] += wa * bnt.f[c];
-          for (int ci = 0; ci < 3; ++ci) {
-            const float* pn = &wn.f[((size_t)c * 3 + ci) * 49];
-            double* pv = &V[(((size_t)m * 3 + ci) * 49 + ab) * 49];
-            for (int ef = 0; ef < 49; ++ef) pv[ef] += wa * pn[ef];
-          }
-        }
-    // tap a of a class (offset a - 3 from p) is valid iff p + a - 3 lies in [0, L)
-    auto valid = [&](int cls1, int a) {
-      const int p = cls1 < 3 ? cls1 : (cls1 == 3 ? 3 : L - 7 + cls1);
-      const int q = p + a - 3;
-      return cls1 == 3 || (q >= 0 && q < L);
-    };
-    const size_t per_cls = (size_t)3 * 13 * M32 * 1024;
-    std::vector<_Float16> g(49 * per_cls, (_Float16)0.f);
-    std::vector<float> rs((size_t)49 * MP, 0.f), cb((size_t)49 * MP, 0.f);
-    std::vector<double> K((size_t)Co * 3 * 169);
-    for (int cls = 0; cls < 49; ++cls) {
-      const int cy = cls / 7, cx = cls % 7;
-      std::fill(K.begin(), K.end(), 0.0);
-      for (int m = 0; m < Co; ++m) {
-        double cbv = bit.f[m];
-        for (int a = 0; a < 7; ++a)
-          for (int b = 0; b < 7; ++b) {
-            if (!valid(cy, a) || !valid(cx, b)) continue;
-            cbv += U[(size_t)m * 49 + a * 7 + b];
-            for (int ci = 0; ci < 3; ++ci) {
-              const double* pv = &V[(((size_t)m * 3 + ci) * 49 + a * 7 + b) * 49];
-              double* pk = &K[((size_t)m * 3 + ci) * 169];
-              for (int e = 0; e < 7; ++e)
-                for (int f = 0; f < 7; ++f) pk[(a + e) * 13 + (b + f)] += pv[e * 7 + f];
-            }
-          }
-        cb[(size_t)cls * MP + m] = (float)cbv;
-        double mx = 0.0;
-        for (int k = 0; k < 3 * 169; ++k) mx = std::max(mx, std::fabs(K[(size_t)m * 3 * 169 + k]));
-        int e2 = 0;
-        if (mx > 0.0) { std::frexp(mx, &e2); e2 = 15 - e2; }
-        rs[(size_t)cls * MP + m] = std::ldexp(1.f, -e2);
-        for (int ci = 0; ci < 3; ++ci)
-          for (int dy = 0; dy < 13; ++dy)
-            for (int dx = 0; dx < 13; ++dx) {
-              const float v = (float)std::ldexp(K[((size_t)m * 3 + ci) * 169 + dy * 13 + dx], e2);
-              const int ks = ci * 13 + dy, m32 = m / 32, lane = (m % 32) + 32 * (dx / 8), e = dx % 8;
-              const size_t base = (size_t)cls * per_cls + ((size_t)ks * M32 + m32) * 1024;
-              const _Float16 hi = (_Float16)v;
-              g[base + lane * 8 + e] = hi;
-              g[base + 512 + lane * 8 + e] = (_Float16)(v - (float)hi);
-            }
-      }
-    }
-    xpw.w = dmalloc(g.size() * sizeof(_Float16));
-    HIPCHK(hipMemcpy(xpw.w, g.data(), g.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    xpw.rs = dmalloc(rs.size() * sizeof(float));
-    HIPCHK(hipMemcpy(xpw.rs, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
-    xpw.cb = dmalloc(cb.size() * sizeof(float));
-    HIPCHK(hipMemcpy(xpw.cb, cb.data(), cb.size() * sizeof(float), hipMemcpyHostToDevice));
+    const XPathPack x = pack_xpath(wn.f, H("init_noise_conv.bias").f, wi.f, H("init_conv.bias").f, Cm, Co, Cin, cfg.latent);
     // the fea branch alone: init_conv.weight[:, Cm:]
-    HostTensor fw;
-    fw.shape = {Co, (int64_t)(Cin - Cm), 1, 7, 7};
-    fw.f.resize((size_t)Co * (Cin - Cm) * 49);
-    for (int m = 0; m < Co; ++m)
-      std::copy(wi.f.begin() + ((size_t)m * Cin + Cm) * 49, wi.f.begin() + ((size_t)m * Cin + Cin) * 49,
-                fw.f.begin() + (size_t)m * (Cin - Cm) * 49);
-    host["init_conv.weight#fea"] = std::move(fw);
-    xpath_ready = true;
-    return xpw;
+    host["init_conv.weight#fea"] = HostTensor{split_channels(wi.f, Co, Cin, 49, Cm, Cin), {}, {Co, (int64_t)(Cin - Cm), 1, 7, 7}};
+    return xpw = {upload(x.g), upload(x.rs), upload(x.cb)};
   }
 
-  // init_noise_conv for the fused conv + maxpool kernel (noise_pool_x3_kernel): A fragments
-  // [kstep = (ci, row pair)][m32][hi|lo][lane][8], k = 8*(lane >> 5) + e -> (dy = 2*pair +
-  // (lane >> 5), dx = e), zero for dy or dx = 7; rows scaled by 2^s(m).
+  // init_noise_conv for the fused conv + maxpool kernel (noise_pool_x3_kernel, pack_conv7c3)
   XPathW npw, c7w;
-  bool noise_pool_ready = false, c7_ready = false;
   const XPathW& Pnoise_pool() {
-    if (!noise_pool_ready) npw = pack_conv7c3(H("init_noise_conv.weight"), "init_noise_conv");
-    noise_pool_ready = true;
+    if (!npw.w) npw = upload_conv7c3(H("init_noise_conv.weight"), "init_noise_conv");
     return npw;
   }
   // init_conv's x half (init_conv.weight#x, ada_u22 / wo_ref) in the same layout (conv7c3_x3_kernel)
   const XPathW& Pconv7c3() {
-    if (!c7_ready) {
+    if (!c7w.w) {
       split_init_conv(3);
-      c7w = pack_conv7c3(H("init_conv.weight#x"), "init_conv x-branch");
+      c7w = upload_conv7c3(H("init_conv.weight#x"), "init_conv x-branch");
     }
-    c7_ready = true;
     return c7w;
   }
   bool conv7c3_on(const View& out) const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_C7"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_C7");
     return !off && x3_convs() && out.H % 32 == 0 && out.W == out.H && out.C % 64 == 0;
   }
-  XPathW pack_conv7c3(const HostTensor& wn, const char* what) {  // [Cm][3][1][7][7]
-    const int Cm = (int)wn.shape[0], M32 = (Cm + 31) / 32;
+  XPathW upload_conv7c3(const HostTensor& wn, const char* what) {  // [Cm][3][1][7][7]
     REQUIRE(wn.shape[1] == 3 && wn.shape.back() == 7, std::string(what) + ": expected a 3 -> C (1,7,7) conv");
-    XPathW pw;
-    std::vector<_Float16> g((size_t)12 * M32 * 1024, (_Float16)0.f);
-    std::vector<float> rs(M32 * 32, 0.f);
-    for (int m = 0; m < Cm; ++m) {
-      float mx = 0.f;
-      for (int k = 0; k < 147; ++k) mx = std::max(mx, std::fabs(wn.f[(size_t)m * 147 + k]));
-      int e2 = 0;
-      if (mx > 0.f) { std::frexp(mx, &e2); e2 = 15 - e2; }
-      rs[m] = std::ldexp(1.f, -e2);
-      for (int ci = 0; ci < 3; ++ci)
-        for (int dy = 0; dy < 7; ++dy)
-          for (int dx = 0; dx < 7; ++dx) {
-            const float v = std::ldexp(wn.f[(((size_t)m * 3 + ci) * 7 + dy) * 7 + dx], e2);
-            const int ks = ci * 4 + dy / 2, lane = (m % 32) + 32 * (dy % 2);
-            const size_t base = ((size_t)ks * M32 + m / 32) * 1024;
-            const _Float16 hi = (_Float16)v;
-            g[base + lane * 8 + dx] = hi;
-            g[base + 512 + lane * 8 + dx] = (_Float16)(v - (float)hi);
-          }
-    }
-    pw.w = dmalloc(g.size() * sizeof(_Float16));
-    HIPCHK(hipMemcpy(pw.w, g.data(), g.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    pw.rs = dmalloc(rs.size() * sizeof(float));
-    HIPCHK(hipMemcpy(pw.rs, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
-    return pw;
+    const Frags c = pack_conv7c3(wn.f, (int)wn.shape[0]);
+    return {upload(c.g), upload(c.rs), nullptr};
   }
   bool noise_pool_enabled() const {
     return xpath_enabled() && cfg.arch == EXTDM_ARCH_U12 && cfg.latent <= 32 && cfg.latent % 2 == 0;
   }
 
   // init_conv's cond_fea branch over F at fea_size instead of its bilinear x2 upsample
-  // (fea_x3.hip header, u12:1034-1041): the 5x5 phase kernels [4 Co][Cf][5][5] (packed by P as
-  // "init_conv.weight#fea5"), the f16x3 edge-line weights and the fp32 corner weights, composed
-  // in fp64. EXTDM_NO_FEA_PHASE=1: the bilinear launch and the 7x7 over the upsampled map (A/B).
+  // (fea_x3.hip header, pack_fea_phase; the 5x5 phase kernels go through P as "init_conv.weight#fea5").
+  // EXTDM_NO_FEA_PHASE=1: the bilinear launch and the 7x7 over the upsampled map (A/B).
   struct FeaPhaseW { void* side = nullptr; float* side_scale = nullptr; float* corner = nullptr; };
   FeaPhaseW fpw;
-  bool fea_phase_ready = false;
   bool fea_phase_enabled() const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_FEA_PHASE"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_FEA_PHASE");
     const int fs = cfg.fea_size;
     return !off && xpath_enabled() && cfg.dim == 64 && cfg.latent == 2 * fs && (fs == 16 || fs == 32) &&
            fea_edges_supported(cfg.fea_ch, cfg.dim, fs);
@@ -583,137 +310,15 @@ struct ExtdmHandle {
     fea_phase_state = ok ? 1 : 0;
     return ok;
   }
-  // up2 of a length-n axis, align_corners=False, as F.interpolate: weight of F[k] in row r
-  // (0 outside [0, 2n): the 7x7's zero padding), and the unclamped interpolation of the
-  // zero-padded F (any integer r)
-  static double up_true(int r, int k, int n) {
-    if (r < 0 || r >= 2 * n) return 0.0;
-    const double src = std::max(0.0, (r + 0.5) * 0.5 - 0.5);
-    const int k0 = (int)src, k1 = k0 < n - 1 ? k0 + 1 : k0;
-    const double lam = src - k0;
-    return (k == k0 ? 1.0 - lam : 0.0) + (k == k1 ? lam : 0.0);
-  }
-  static double up_inf(int r, int k) {
-    const int j = (r >= 0 ? r : r - 1) / 2;  // floor(r / 2)
-    if (k == j) return 0.75;
-    return (r - 2 * j == 0 ? k == j - 1 : k == j + 1) ? 0.25 : 0.0;
-  }
   const FeaPhaseW& Pfea_phase() {
-    if (fea_phase_ready) return fpw;
+    if (fpw.side) return fpw;
     Pxpath();  // the fea half of init_conv.weight
     const HostTensor& wt = H("init_conv.weight#fea");  // [Co][Cf][1][7][7]
-    const int Co = (int)wt.shape[0], Cf = (int)wt.shape[1], n = cfg.fea_size;
+    const int Co = (int)wt.shape[0], Cf = (int)wt.shape[1];
     REQUIRE(wt.shape.back() == 7 && Co == cfg.dim && Cf % 16 == 0, "phase-composed init_conv: unexpected weight");
-    auto W = [&](int co, int ci, int dy, int dx) { return (double)wt.f[(((size_t)co * Cf + ci) * 7 + dy) * 7 + dx]; };
-    // interior composition A[p][l][d]: weight of tap l (F[m - 2 + l]) in row 2m + p + d - 3 (any m)
-    double A[2][5][7];
-    for (int p = 0; p < 2; ++p)
-      for (int l = 0; l < 5; ++l)
-        for (int d = 0; d < 7; ++d) A[p][l][d] = up_inf(2 * 8 + p + d - 3, 8 - 2 + l);
-    // edge deltas: U - Uinf at column ke of output row r (nonzero for ke = 0 / n - 1 only)
-    auto delta = [&](int r, int ke) { return up_true(r, ke, n) - up_inf(r, ke); };
-    // main 5x5 phase kernels, row ph * Co + co, ph = 2 py + px
-    {
-      HostTensor k5;
-      k5.shape = {4 * (int64_t)Co, Cf, 1, 5, 5};
-      k5.f.assign((size_t)4 * Co * Cf * 25, 0.f);
-      std::vector<double> t(7 * 5);
-      for (int co = 0; co < Co; ++co)
-        for (int ci = 0; ci < Cf; ++ci)
-          for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-              // t[dy][lx] = sum_dx W[dy][dx] A[px][lx][dx]
-              for (int dy = 0; dy < 7; ++dy)
-                for (int lx = 0; lx < 5; ++lx) {
-                  double s_ = 0.0;
-                  for (int dx = 0; dx < 7; ++dx) s_ += W(co, ci, dy, dx) * A[px][lx][dx];
-                  t[dy * 5 + lx] = s_;
-                }
-              for (int ly = 0; ly < 5; ++ly)
-                for (int lx = 0; lx < 5; ++lx) {
-                  double s_ = 0.0;
-                  for (int dy = 0; dy < 7; ++dy) s_ += A[py][ly][dy] * t[dy * 5 + lx];
-                  k5.f[((((size_t)(2 * py + px) * Co + co) * Cf + ci) * 5 + ly) * 5 + lx] = (float)s_;
-                }
-            }
-      host["init_conv.weight#fea5"] = std::move(k5);
-    }
-    // edge lines: [pair][side][row m = co * 8 + (d*2 + py)*2 + px][ci][tap], then f16x3-packed
-    const int R = 8 * Co, MT = (R + 127) / 128, RP = MT * 128, ncb = Cf / 16;
-    std::vector<double> ws((size_t)4 * R * Cf * 5, 0.0);
-    for (int pair = 0; pair < 2; ++pair)
-      for (int side = 0; side < 2; ++side) {
-        const int ke = side ? n - 1 : 0, base = side ? 2 * n - 4 : 0;
-        for (int d = 0; d < 2; ++d)
-          for (int py = 0; py < 2; ++py)
-            for (int px = 0; px < 2; ++px) {
-              // pair 0: output row y = base + 2d + py (the delta axis), columns by phase px;
-              // pair 1: output column x = base + 2d + px, rows by phase py
-              const int e = base + 2 * d + (pair ? px : py), ip = pair ? py : px;
-              double dl[7];
-              for (int k = 0; k < 7; ++k) dl[k] = delta(e + k - 3, ke);
-              for (int co = 0; co < Co; ++co) {
-                const int m = co * 8 + (d * 2 + py) * 2 + px;  // fea_x3.hip row order
-                for (int ci = 0; ci < Cf; ++ci)
-                  for (int l = 0; l < 5; ++l) {
-                    double s_ = 0.0;
-                    for (int dy = 0; dy < 7; ++dy)
-                      for (int dx = 0; dx < 7; ++dx)
-                        s_ += W(co, ci, dy, dx) * (pair ? dl[dx] * A[ip][l][dy] : dl[dy] * A[ip][l][dx]);
-                    ws[((((size_t)pair * 2 + side) * R + m) * Cf + ci) * 5 + l] = s_;
-                  }
-              }
-            }
-      }
-    const size_t ah = (size_t)5 * 4 * 2 * 512;  // halves per (mtile, cb): [tap][m32][hl][lane][8]
-    std::vector<_Float16> g((size_t)4 * MT * ncb * ah, (_Float16)0.f);
-    std::vector<float> rs((size_t)4 * RP, 1.f);
-    for (int ps = 0; ps < 4; ++ps)
-      for (int m = 0; m < R; ++m) {
-        double mx = 0.0;
-        for (size_t k = 0; k < (size_t)Cf * 5; ++k) mx = std::max(mx, std::fabs(ws[((size_t)ps * R + m) * Cf * 5 + k]));
-        int e2 = 0;
-        if (mx > 0.0) { std::frexp(mx, &e2); e2 = 15 - e2; }
-        rs[(size_t)ps * RP + m] = std::ldexp(1.f, -e2);
-        const int mtile = m / 128, m32 = (m % 128) / 32, lc = m % 32;
-        for (int ci = 0; ci < Cf; ++ci)
-          for (int l = 0; l < 5; ++l) {
-            const float v = (float)std::ldexp(ws[(((size_t)ps * R + m) * Cf + ci) * 5 + l], e2);
-            const int cb = ci / 16, lane = lc + 32 * ((ci % 16) / 8), e = ci % 8;
-            const size_t b0 = ((((size_t)ps * MT + mtile) * ncb + cb) * ah) + (size_t)((l * 4 + m32) * 2) * 512;
-            const _Float16 hi = (_Float16)v;
-            g[b0 + lane * 8 + e] = hi;
-            g[b0 + 512 + lane * 8 + e] = (_Float16)(v - (float)hi);
-          }
-      }
-    fpw.side = dmalloc(g.size() * sizeof(_Float16));
-    HIPCHK(hipMemcpy(fpw.side, g.data(), g.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    fpw.side_scale = dmalloc(rs.size() * sizeof(float));
-    HIPCHK(hipMemcpy(fpw.side_scale, rs.data(), rs.size() * sizeof(float), hipMemcpyHostToDevice));
-    // corners [corner = 2 (bottom) + (right)][ci][co][p = yy * 4 + xx]
-    std::vector<float> cw((size_t)4 * 16 * Cf * Co, 0.f);
-    for (int corner = 0; corner < 4; ++corner) {
-      const int ky = (corner >> 1) ? n - 1 : 0, kx = (corner & 1) ? n - 1 : 0;
-      const int yb = (corner >> 1) ? 2 * n - 4 : 0, xb = (corner & 1) ? 2 * n - 4 : 0;
-      for (int p = 0; p < 16; ++p) {
-        double dy_[7], dx_[7];
-        for (int k = 0; k < 7; ++k) {
-          dy_[k] = delta(yb + p / 4 + k - 3, ky);
-          dx_[k] = delta(xb + p % 4 + k - 3, kx);
-        }
-        for (int ci = 0; ci < Cf; ++ci)
-          for (int co = 0; co < Co; ++co) {
-            double s_ = 0.0;
-            for (int dy = 0; dy < 7; ++dy)
-              for (int dx = 0; dx < 7; ++dx) s_ += W(co, ci, dy, dx) * dy_[dy] * dx_[dx];
-            cw[(((size_t)corner * Cf + ci) * Co + co) * 16 + p] = (float)s_;
-          }
-      }
-    }
-    fpw.corner = dmalloc(cw.size() * sizeof(float));
-    HIPCHK(hipMemcpy(fpw.corner, cw.data(), cw.size() * sizeof(float), hipMemcpyHostToDevice));
-    fea_phase_ready = true;
-    return fpw;
+    FeaPhasePack fp = pack_fea_phase(wt.f, Co, Cf, cfg.fea_size);
+    host["init_conv.weight#fea5"] = HostTensor{std::move(fp.k5), {}, {4 * (int64_t)Co, Cf, 1, 5, 5}};
+    return fpw = {upload(fp.side), upload(fp.side_scale), upload(fp.corner)};
   }
   // rp += init_conv's cond_fea branch of F [B][Cf][tp][fs][fs] (phase-composed)
   void fea_phase_conv(const View& rp, const View& f) {
@@ -736,7 +341,7 @@ struct ExtdmHandle {
   // term once over the tp predicted frames (fr_all); each step adds it to the x-branch. u12's
   // branch reads TrajWarp(x) and stays in the step. EXTDM_NO_FEA_HOIST=1: the per-step conv (A/B).
   bool fea_hoist_on() const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_FEA_HOIST"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_FEA_HOIST");
     if (off) return false;
     if (cfg.arch == EXTDM_ARCH_ADA_U22 || cfg.arch == EXTDM_ARCH_WO_REF) return true;
     return cfg.arch == EXTDM_ARCH_ADA && xpath_enabled();  // ada: added in the x-branch kernel's epilogue
@@ -746,18 +351,13 @@ struct ExtdmHandle {
     if (has("init_conv.weight#x")) return;
     const HostTensor& w = H("init_conv.weight");
     const int Co = (int)w.shape[0], Cin = (int)w.shape[1];
-    size_t kk = 1;
-    for (size_t i = 2; i < w.shape.size(); ++i) kk *= (size_t)w.shape[i];
+    int kk = 1;
+    for (size_t i = 2; i < w.shape.size(); ++i) kk *= (int)w.shape[i];
     REQUIRE(c0 > 0 && c0 < Cin, "init_conv split: bad channel count");
     for (int part = 0; part < 2; ++part) {
       const int lo = part ? c0 : 0, hi = part ? Cin : c0;
-      HostTensor t;
-      t.shape = w.shape;
+      HostTensor t{split_channels(w.f, Co, Cin, kk, lo, hi), {}, w.shape};
       t.shape[1] = hi - lo;
-      t.f.resize((size_t)Co * (hi - lo) * kk);
-      for (int m = 0; m < Co; ++m)
-        std::copy(w.f.begin() + ((size_t)m * Cin + lo) * kk, w.f.begin() + ((size_t)m * Cin + hi) * kk,
-                  t.f.begin() + (size_t)m * (hi - lo) * kk);
       host[part ? "init_conv.weight#f" : "init_conv.weight#x"] = std::move(t);
     }
   }
@@ -931,8 +531,7 @@ struct ExtdmHandle {
             t[(((size_t)pat * nh + hd) * 32 + i) * 32 + j] = v * s2;
           }
     }
-    float* d = dmalloc(t.size() * 4);
-    HIPCHK(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    float* d = upload(t);
     mask_bias[key] = {d, npat};
     return d;
   }
@@ -974,8 +573,7 @@ struct ExtdmHandle {
             t[(((size_t)pat * nh + hd) * 64 + i) * 64 + j] = v * s2;
           }
     }
-    float* d = dmalloc(t.size() * 4);
-    HIPCHK(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    float* d = upload(t);
     mask_bias[key] = {d, npat};
     return d;
   }
@@ -996,8 +594,7 @@ struct ExtdmHandle {
           t[((size_t)hd * 32 + i) * 32 + j] =
               (pi != pj || tj >= g.D) ? -INFINITY : time_bias_host[(size_t)hd * 1024 + ti * 32 + tj] * s2;
         }
-    float* d = dmalloc(t.size() * 4);
-    HIPCHK(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    float* d = upload(t);
     mask_bias[key] = {d, 1};
     return d;
   }
@@ -1015,158 +612,45 @@ struct ExtdmHandle {
       for (int i = 0; i < 64; ++i)
         for (int j = 0; j < 64; ++j)
           t[((size_t)hd * 64 + i) * 64 + j] = j >= g.D ? -INFINITY : time_bias_host[((size_t)hd * 64 + i) * 64 + j] * s2;
-    float* d = dmalloc(t.size() * 4);
-    HIPCHK(hipMemcpy(d, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    float* d = upload(t);
     mask_bias[key] = {d, 1};
     return d;
   }
 
-  // Packed weights of the fused attention kernels (stw_fused.hip header): qkv rows
-  // in 32-row units (one head of dim 32 / two heads of dim 16).
-  float* packed_stw_qkv(const std::string& n) {
-    auto it = dev.find(n + "#stwqkv");
+  // Packed weights of the fused attention kernels (stw_fused.hip header; pack_stw_rows): the qkv
+  // weight (nmat 3) or the projection (nmat 1)
+  float* packed_stw(const std::string& n, int nmat) {
+    const std::string key = n + (nmat == 3 ? "#stwqkv" : "#stwproj");
+    auto it = dev.find(key);
     if (it != dev.end()) return it->second;
     const HostTensor& t = H(n);
-    const int C = (int)t.shape[1], hid = cfg.heads * cfg.dim_head, units = hid / 32;
-    REQUIRE((int)t.shape[0] == 3 * hid, "qkv weight rows != 3 * heads * dim_head: " + n);
-    std::vector<float> a((size_t)units * (C / 2) * 3 * 64);
-    for (int u = 0; u < units; ++u)
-      for (int s2 = 0; s2 < C / 2; ++s2)
-        for (int wh = 0; wh < 3; ++wh)
-          for (int l = 0; l < 64; ++l)
-            a[(((size_t)u * (C / 2) + s2) * 3 + wh) * 64 + l] =
-                t.f[(size_t)(wh * hid + u * 32 + (l & 31)) * C + 2 * s2 + (l >> 5)];
-    float* d = dmalloc(a.size() * 4);
-    HIPCHK(hipMemcpy(d, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    return dev[n + "#stwqkv"] = d;
+    REQUIRE(nmat == 1 || (int)t.shape[0] == 3 * cfg.heads * cfg.dim_head, "qkv weight rows != 3 * heads * dim_head: " + n);
+    return dev[key] = upload(pack_stw_rows(t.f, nmat, (int)t.shape[0] / nmat, (int)t.shape[1]));
   }
-  float* packed_stw_proj(const std::string& n) {
-    auto it = dev.find(n + "#stwproj");
-    if (it != dev.end()) return it->second;
-    const HostTensor& t = H(n);
-    const int C = (int)t.shape[0], K = (int)t.shape[1];
-    std::vector<float> a((size_t)(C / 32) * (K / 2) * 64);
-    for (int tl = 0; tl < C / 32; ++tl)
-      for (int s2 = 0; s2 < K / 2; ++s2)
-        for (int l = 0; l < 64; ++l)
-          a[((size_t)tl * (K / 2) + s2) * 64 + l] = t.f[(size_t)(tl * 32 + (l & 31)) * K + 2 * s2 + (l >> 5)];
-    float* d = dmalloc(a.size() * 4);
-    HIPCHK(hipMemcpy(d, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    return dev[n + "#stwproj"] = d;
-  }
-  // f16x3 attention weights (stw_x3.hip): per unit u of 32 qkv rows, fragments of
-  // [hi|lo][lane][8] for q, k, v (row u*32 + lc, channels 16s + 8h + e) and the
-  // projection (row ct*32 + lc, hid u*32 + 16s' + 8(e>>2) + 4h + (e&3): the row order
-  // of the O^T accumulator). Each matrix is scaled by one power of two.
-  // sc: [q, k, v, proj factors, softmax exp2 factor] (stw_x3.hip kernel header); s2 =
-  // 2^(e_q + e_k), the factor of the scores (and of their bias / mask table)
+  // f16x3 attention weights (stw_x3.hip; pack_attn_x3); nb empty: a norm without a bias
   struct AttnX3W { void* w = nullptr; float* sc = nullptr; float s2 = 1.f; };
   std::unordered_map<std::string, AttnX3W> attn_x3w;
-  static float pow2_scale(const float* p, size_t n, float& inv) {
-    float mx = 0.f;
-    for (size_t i = 0; i < n; ++i) mx = std::max(mx, std::fabs(p[i]));
-    int e = 0;
-    if (mx > 0.f) { std::frexp(mx, &e); e = 15 - e; }
-    inv = std::ldexp(1.f, -e);
-    return std::ldexp(1.f, e);
-  }
-  // ng / nb: the affine of the norm whose output the kernel splits (MODE 0: the PreNorm
-  // gamma; MODE 1: the inner LayerNorm's weight and bias; nb empty without a bias)
-  static int pow2_exp(double v) {  // e with v * 2^e in [1, 2), clamped; 0 for v == 0
-    if (!(v > 0.0) || !std::isfinite(v)) return 0;
-    int e = 0;
-    std::frexp(v, &e);
-    return std::min(30, std::max(-30, 1 - e));
-  }
   const AttnX3W& packed_attn_x3(const std::string& nqkv, const std::string& nproj, const std::string& ng,
                                 const std::string& nb) {
     auto it = attn_x3w.find(nqkv);
     if (it != attn_x3w.end()) return it->second;
     const HostTensor& tq = H(nqkv);
     const HostTensor& tp = H(nproj);
-    const int C = (int)tq.shape[1], hid = cfg.heads * cfg.dim_head, units = hid / 32;
+    const HostTensor& tg = H(ng);
+    const int C = (int)tq.shape[1], hid = cfg.heads * cfg.dim_head, uh = attn_x3_unit_halves(C);
     REQUIRE((int)tq.shape[0] == 3 * hid && (int)tp.shape[0] == C && (int)tp.shape[1] == hid,
             "attention weight shapes: " + nqkv);
-    const int KS = C / 16, CT = C / 32, uh = attn_x3_unit_halves(C);
     REQUIRE(uh > 0, "attention x3 layout: unsupported channel count");
-    float inv[4], sc[4];
-    for (int m = 0; m < 3; ++m) sc[m] = pow2_scale(tq.f.data() + (size_t)m * hid * C, (size_t)hid * C, inv[m]);
-    sc[3] = pow2_scale(tp.f.data(), tp.f.size(), inv[3]);
-    std::vector<_Float16> a((size_t)units * uh);
-    auto put = [&](size_t frag_base, int l, int e, float v) {
-      const _Float16 hi = (_Float16)v;
-      a[frag_base + l * 8 + e] = hi;
-      a[frag_base + 512 + l * 8 + e] = (_Float16)(v - (float)hi);
-    };
-    for (int u = 0; u < units; ++u) {
-      const size_t ub = (size_t)u * uh;
-      for (int m = 0; m < 3; ++m)
-        for (int s2 = 0; s2 < KS; ++s2)
-          for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-              const int row = m * hid + u * 32 + (l & 31), c = 16 * s2 + 8 * (l >> 5) + e;
-              put(ub + ((size_t)m * KS + s2) * 1024, l, e, tq.f[(size_t)row * C + c] * sc[m]);
-            }
-      for (int ct = 0; ct < CT; ++ct)
-        for (int s2 = 0; s2 < 2; ++s2)
-          for (int l = 0; l < 64; ++l)
-            for (int e = 0; e < 8; ++e) {
-              const int c = ct * 32 + (l & 31);
-              const int hd = u * 32 + 16 * s2 + 8 * (e >> 2) + 4 * (l >> 5) + (e & 3);
-              put(ub + ((size_t)3 * KS + ct * 2 + s2) * 1024, l, e, tp.f[(size_t)c * hid + hd] * sc[3]);
-            }
-    }
-    // Operand exponents (stw_x3.hip kernel header). Relative to a split input of largest
-    // |value| in [1, 2) (the kernel's 2^e_w carries a further 2^8, folded back through the
-    // factors below); channel c of it is then ~ (|g_c| + |b_c|) * 2^e_x / 4 (e_x
-    // brings the largest affine to [1, 2); a unit-variance z peaks near 4). e_q / e_k / e_v
-    // bring the largest expected row norm of q * q_scale, k, v (weights times those channel
-    // scales) to [1, 2). Powers of two: the scaling itself is exact.
-    const HostTensor& tg = H(ng);
     REQUIRE((int)tg.f.size() == C, "attention norm affine size: " + ng);
-    std::vector<double> sx(C);
-    double mx = 0.0;
-    for (int c = 0; c < C; ++c) {
-      sx[c] = std::fabs((double)tg.f[c]) + (nb.empty() ? 0.0 : std::fabs((double)H(nb).f[c]));
-      mx = std::max(mx, sx[c]);
-    }
-    const int ex = pow2_exp(mx);
-    int em[3];
-    for (int m = 0; m < 3; ++m) {
-      double best = 0.0;
-      for (int d = 0; d < hid; ++d) {
-        double n2 = 0.0;
-        for (int c = 0; c < C; ++c) {
-          const double w = (double)tq.f[((size_t)m * hid + d) * C + c] * std::ldexp(sx[c], ex) * 0.25;
-          n2 += w * w;
-        }
-        best = std::max(best, std::sqrt(n2));
-      }
-      // to [2^4, 2^5) for q and k, [2^2, 2^3) for v: values down to 2^-7 / 2^-5 of the typical
-      // one keep a normal lo, with headroom to 65504 (O = P' v' <= 16 max|v'| with P' = 16 P)
-      em[m] = pow2_exp(best * (m == 0 ? (double)q_scale() : 1.0)) + (m < 2 ? 4 : 2);
-    }
-    float scv[5];
-    scv[0] = std::ldexp(inv[0], em[0]);
-    scv[1] = std::ldexp(inv[1], em[1]);
-    scv[2] = std::ldexp(inv[2], em[2]);
-    scv[3] = std::ldexp(inv[3], -(em[2] + 4));
-    scv[4] = (float)std::ldexp(1.4426950408889634, -(em[0] + em[1]));
-    AttnX3W r;
-    r.s2 = std::ldexp(1.f, em[0] + em[1]);
-    r.w = dmalloc(a.size() * sizeof(_Float16));
-    HIPCHK(hipMemcpy(r.w, a.data(), a.size() * sizeof(_Float16), hipMemcpyHostToDevice));
-    r.sc = dmalloc(5 * sizeof(float));
-    HIPCHK(hipMemcpy(r.sc, scv, 5 * sizeof(float), hipMemcpyHostToDevice));
-    return attn_x3w[nqkv] = r;
+    const AttnX3Pack a = pack_attn_x3(tq.f, tp.f, tg.f, nb.empty() ? nullptr : &H(nb).f, C, hid, uh, q_scale());
+    return attn_x3w[nqkv] = {upload(a.a), upload(std::vector<float>(a.sc, a.sc + 5)), a.s2};
   }
   // f16x3 convolutions (F16X3, and BF16_ATTN, whose attention core alone is bf16)
   bool x3_convs() const { return cfg.precision == EXTDM_PRECISION_F16X3 || cfg.precision == EXTDM_PRECISION_BF16_ATTN; }
   bool bf16_attn() const { return cfg.precision == EXTDM_PRECISION_BF16_ATTN; }
   bool x3_attn_ok(int C, int ntok, int mode) const {
-    auto flag = [](const char* n) { const char* v = getenv(n); return v && v[0] && v[0] != '0'; };
     // read per call: EXTDM_NO_X3_ATTN / _STW / _TEMPORAL route a layer back to the fp32 kernels
-    const bool off = flag("EXTDM_NO_X3_ATTN"), off_stw = flag("EXTDM_NO_X3_STW"), off_tmp = flag("EXTDM_NO_X3_TEMPORAL");
+    const bool off = env_flag("EXTDM_NO_X3_ATTN"), off_stw = env_flag("EXTDM_NO_X3_STW"), off_tmp = env_flag("EXTDM_NO_X3_TEMPORAL");
     if (off || (mode == 0 && off_stw) || (mode == 1 && off_tmp)) return false;
     // BF16_ATTN: the same fused kernels with the bf16 attention core (dim_head 32)
     return (cfg.precision == EXTDM_PRECISION_F16X3 || (bf16_attn() && cfg.dim_head == 32)) &&
@@ -1175,11 +659,11 @@ struct ExtdmHandle {
   // the fused 64-token-window route (stw64_x3.hip) in F16X3 and BF16_ATTN; EXTDM_NO_STW64=1 sends
   // those windows back to the core route / fp32 fused kernels (A/B)
   bool stw64_ok(int C, int ntok) const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_STW64"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_STW64");
     return !off && x3_convs() && stw64_x3_supported(C, ntok, cfg.dim_head, cfg.heads);
   }
   bool fused_ok(int C, int ntok) const {
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_FUSED_STW"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_FUSED_STW");
     return !off && fused_attn_supported(C, ntok, cfg.dim_head, cfg.heads);
   }
   // the unfused core path (LN -> qkv 1x1 conv -> attn_core.hip -> proj 1x1 conv + residual): for
@@ -1189,7 +673,7 @@ struct ExtdmHandle {
   bool core_attn(int ntok, int max_tok, bool fused_x3, bool window) const {
     if (!(cfg.dim_head == 32 || (cfg.dim_head == 16 && window && !bf16_attn())) || ntok > max_tok) return false;
     if (bf16_attn()) return !fused_x3;
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_X3_CORE"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_X3_CORE");
     return cfg.precision == EXTDM_PRECISION_F16X3 && !fused_x3 && !off;
   }
   float q_scale() const { return 1.0f / std::sqrt((float)cfg.dim_head); }
@@ -1257,8 +741,8 @@ struct ExtdmHandle {
     }
     if (fused_ok(x.C, N)) {
       const std::string a = p + ".fn.fn.attn";
-      float* wq = packed_stw_qkv(a + ".qkv.weight");
-      float* wp = packed_stw_proj(a + ".proj.weight");
+      float* wq = packed_stw(a + ".qkv.weight", 3);
+      float* wp = packed_stw(a + ".proj.weight", 1);
       if (plan) return;
       REQUIRE(stw_fused(s, x, g, cfg.heads, cfg.dim_head, D(p + ".fn.norm.gamma"), wq, wp, D(a + ".proj.bias"),
                         bias_dense.at(p), bstride, rope_cos, rope_sin, q_scale()),
@@ -1290,8 +774,7 @@ struct ExtdmHandle {
     REQUIRE(T <= 64 && tb_stride == 64, "temporal attention over more than 64 frames");
     g.per = 64;
     const bool x3 = cfg.precision == EXTDM_PRECISION_F16X3 || (bf16_attn() && cfg.dim_head == 32);
-    auto flag = [](const char* n) { const char* v = getenv(n); return v && v[0] && v[0] != '0'; };
-    if (x3 && !flag("EXTDM_NO_T64") && !flag("EXTDM_NO_X3_ATTN") && !flag("EXTDM_NO_X3_TEMPORAL") &&
+    if (x3 && !env_flag("EXTDM_NO_T64") && !env_flag("EXTDM_NO_X3_ATTN") && !env_flag("EXTDM_NO_X3_TEMPORAL") &&
         temporal64_x3_supported(x.C, T, cfg.dim_head, cfg.heads) && out.sb == x.sb && out.sc == x.sc && out.st == x.st &&
         x.st == (long)x.H * x.W && ((long)(x.C - 1) * x.sc + (long)T * x.st) * 4 < (1L << 30)) {  // 31-bit buffer offsets per sample
       const AttnX3W& w = packed_attn_x3(a + ".attn.to_qkv.weight", a + ".attn.to_out.weight", a + ".norm.weight",
@@ -1303,7 +786,7 @@ struct ExtdmHandle {
               "f16x3 64-slot temporal attention launch rejected");
       return;
     }
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_X3_CORE"); return v && v[0] && v[0] != '0'; }();
+    static const bool off = env_flag("EXTDM_NO_X3_CORE");
     const bool core = bf16_attn() ? cfg.dim_head == 32 : (cfg.precision == EXTDM_PRECISION_F16X3 && !off);
     last_core = core;
     Scope sc(arena);
@@ -1370,8 +853,8 @@ struct ExtdmHandle {
       return;
     }
     if (fused_ok(x.C, T) && T <= 32) {
-      float* wq = packed_stw_qkv(a + ".attn.to_qkv.weight");
-      float* wo = packed_stw_proj(a + ".attn.to_out.weight");
+      float* wq = packed_stw(a + ".attn.to_qkv.weight", 3);
+      float* wo = packed_stw(a + ".attn.to_out.weight", 1);
       if (plan) return;
       REQUIRE(temporal_fused(s, x, out, g, cfg.heads, cfg.dim_head, D(p + ".fn.norm.gamma"), D(a + ".norm.weight"),
                              D(a + ".norm.bias"), wq, wo, time_bias, 32, rope_cos, rope_sin, q_scale()),
@@ -1471,8 +954,8 @@ struct ExtdmHandle {
   }
   // EXTDM_CROSS_STAGED=1: the per-step kernel stages and splits K / V itself (A/B)
   bool kv_split_ok() const {
-    static const bool staged = [] { const char* v = getenv("EXTDM_CROSS_STAGED"); return v && v[0] && v[0] != '0'; }();
-    static const bool off = [] { const char* v = getenv("EXTDM_NO_X3_CROSS"); return v && v[0] && v[0] != '0'; }();
+    static const bool staged = env_flag("EXTDM_CROSS_STAGED");
+    static const bool off = env_flag("EXTDM_NO_X3_CROSS");
     return kvp != nullptr && !staged && !off && x3_convs() && cfg.fea_ch == 32 * kTrajHeads;
   }
   // xq = maxpool(1,2,2) of the tp frames' init_noise_conv output (u12:811)
@@ -1485,7 +968,7 @@ struct ExtdmHandle {
     conv(q, xq, nullptr, P(c + ".linear_q.weight"), 1, 0, D(c + ".linear_q.bias"), nullptr, ACT_RELU);
     View a = alloc_cf(B, C, tp, fs, fs);
     if (!plan) {
-      static const bool off = [] { const char* v = getenv("EXTDM_NO_X3_CROSS"); return v && v[0] && v[0] != '0'; }();
+      static const bool off = env_flag("EXTDM_NO_X3_CROSS");
       const bool x3 = !off && x3_convs() &&
                       (kv_split_ok() ? cross_attention_x3p(s, q.p, kvp, a.p, B, C, kTrajHeads, tp * fs * fs, tc * fs * fs)
                                      : cross_attention_x3(s, q.p, kv_k.p, kv_v.p, a.p, B, C, kTrajHeads, tp * fs * fs,
@@ -1808,24 +1291,8 @@ struct ExtdmHandle {
   std::pair<float*, float*> bn(const std::string& p) {
     auto it = dev.find(p + "#bn_a");
     if (it != dev.end()) return {it->second, dev.at(p + "#bn_b")};
-    const auto& w = H(p + ".weight").f;
-    const auto& b = H(p + ".bias").f;
-    const auto& rm = H(p + ".running_mean").f;
-    const auto& rv = H(p + ".running_var").f;
-    std::vector<float> a(w.size()), bb(w.size());
-    for (size_t i = 0; i < w.size(); ++i) {
-      volatile float inv = 1.0f / std::sqrt(rv[i] + 1e-5f);
-      a[i] = inv * w[i];
-      volatile float t = rm[i] * a[i];
-      bb[i] = b[i] - t;
-    }
-    float* da = dmalloc(a.size() * 4);
-    float* db = dmalloc(bb.size() * 4);
-    HIPCHK(hipMemcpy(da, a.data(), a.size() * 4, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(db, bb.data(), bb.size() * 4, hipMemcpyHostToDevice));
-    dev[p + "#bn_a"] = da;
-    dev[p + "#bn_b"] = db;
-    return {da, db};
+    const Affine f = bn_fold_f32(H(p + ".weight").f, H(p + ".bias").f, H(p + ".running_mean").f, H(p + ".running_var").f);
+    return {dev[p + "#bn_a"] = upload(f.a), dev[p + "#bn_b"] = upload(f.b)};
   }
   bool has_decoder() const { return has("generator.first.conv.weight"); }
   bool has_unet() const { return has("init_conv.weight"); }
@@ -2111,8 +1578,7 @@ struct ExtdmHandle {
         sinus[(size_t)(half + i) * NT + t] = std::cos(a);
       }
     }
-    float* d_sin = dmalloc(sinus.size() * sizeof(float));
-    HIPCHK(hipMemcpy(d_sin, sinus.data(), sinus.size() * sizeof(float), hipMemcpyHostToDevice));
+    float* d_sin = upload(sinus);
     float* h1 = dmalloc((size_t)tdim * NT * sizeof(float));
     float* te = dmalloc((size_t)tdim * NT * sizeof(float));
     View vs = cf_view(d_sin, 1, dim, 1, 1, NT);
@@ -2140,9 +1606,8 @@ struct ExtdmHandle {
       std::copy(bb.f.begin(), bb.f.end(), bcat.begin() + film_row[b]);
     }
     if (mtot > 0) {
-      PackedW pw = pack_matrix(wcat, mtot, tdim);
-      float* dbias = dmalloc(bcat.size() * sizeof(float));
-      HIPCHK(hipMemcpy(dbias, bcat.data(), bcat.size() * sizeof(float), hipMemcpyHostToDevice));
+      PackedW pw = gemm_weight(pack_gemm_plane(wcat, mtot, tdim, conv_bm(mtot)), mtot, tdim);
+      float* dbias = upload(bcat);
       film = dmalloc((size_t)mtot * NT * sizeof(float));
       conv(cf_view(film, 1, mtot, 1, 1, NT), vte, nullptr, pw, 1, 0, dbias);
     }
@@ -2159,10 +1624,8 @@ struct ExtdmHandle {
           c[n * rh + i] = std::cos(a);
           sn[n * rh + i] = std::sin(a);
         }
-      rope_cos = dmalloc(c.size() * 4);
-      rope_sin = dmalloc(sn.size() * 4);
-      HIPCHK(hipMemcpy(rope_cos, c.data(), c.size() * 4, hipMemcpyHostToDevice));
-      HIPCHK(hipMemcpy(rope_sin, sn.data(), sn.size() * 4, hipMemcpyHostToDevice));
+      rope_cos = upload(c);
+      rope_sin = upload(sn);
     }
     // window relative-position bias, dense per layer: bias[h][i][j] = table[index[i][j]][h]
     // ([heads][32][32] for windows of <= 32 tokens, [heads][64][64] for 4x4x4 windows).
@@ -2182,9 +1645,7 @@ struct ExtdmHandle {
         for (int i = 0; i < N; ++i)
           for (int j = 0; j < N; ++j)
             d[((size_t)h * st + i) * st + j] = tab.f[(size_t)idx.i[(size_t)i * N + j] * nh + h];
-      float* dd = dmalloc(d.size() * 4);
-      HIPCHK(hipMemcpy(dd, d.data(), d.size() * 4, hipMemcpyHostToDevice));
-      bias_dense[p] = dd;
+      bias_dense[p] = upload(d);
       bias_host[p] = {std::move(d), st};
     }
     // temporal T5 relative-position bias (RelativePositionBias, u12:42-79), max_distance 32
@@ -2213,8 +1674,7 @@ struct ExtdmHandle {
           }
           for (int h = 0; h < nh; ++h) d[((size_t)h * st + i) * st + j] = emb.f[(size_t)bucket * nh + h];
         }
-      time_bias = dmalloc(d.size() * 4);
-      HIPCHK(hipMemcpy(time_bias, d.data(), d.size() * 4, hipMemcpyHostToDevice));
+      time_bias = upload(d);
       time_bias_host = std::move(d);
     }
     HIPCHK(hipDeviceSynchronize());
@@ -2366,21 +1826,8 @@ struct ExtdmHandle {
 };
 
 // ---------------------------------------------------------------- C ABI
-namespace {
-template <class F>
-int guarded(F&& f) {
-  try {
-    f();
-    return 0;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return -1;
-  }
-}
-}  // namespace
-
 namespace extdm {
-// the message of extdm_last_error for entry points outside this file (fvd.cpp; declared in i3d.h)
+// the message of extdm_last_error (declared in host_util.h: guarded() of every runtime sets it)
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 static thread_local std::string g_noted_kernel;
 // kernel-name notes are formatted only inside extdm_bench_layer (NoteScope): the forward's

@@ -25,6 +25,7 @@
 #include <cstdlib>
 
 #include "attn64_core.h"
+#include "host_util.h"
 
 namespace extdm {
 
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(NW * 64) void stw64_x3_kernel(float* x, long sb, lo
 // (whole 4-window groups per window row), 8-B aligned rows; EXTDM_STW64_NO_TILE=1 forces the
 // per-lane path (A/B)
 bool stw64_tile_ok(const View& x, const AttnGeom& g, int groups) {
-  static const bool off = [] { const char* v = getenv("EXTDM_STW64_NO_TILE"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_STW64_NO_TILE");
   return !off && x.C == 64 && g.ws0 == 4 && g.ws1 == 4 && g.ws2 == 4 && g.H == g.Hp && g.W == g.Wp && g.W % 16 == 0 &&
          groups % 4 == 0 && x.st == (long)x.H * x.W && x.sc % 2 == 0 && x.sb % 2 == 0 && x.st % 2 == 0 &&
          ((uintptr_t)x.p & 7) == 0;

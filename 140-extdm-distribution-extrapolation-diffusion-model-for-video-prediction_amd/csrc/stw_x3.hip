@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "attn_x3_ops.h"
+#include "host_util.h"
 
 namespace extdm {
 
@@ -827,8 +828,8 @@ __global__ __launch_bounds__(NW * 64) void attn_x3_kernel(const float* x, float*
 // of 16 / 8 pixels inside a sample, 16-B aligned rows; x and out share their channel / frame
 // strides (temporal_x3). EXTDM_X3_TILE1_16=1: only D = 16, the round-4 scope (A/B).
 bool attn_x3_tile1_ok(const View& x, const View& out, const AttnGeom& g, int groups) {
-  static const bool off = [] { const char* v = getenv("EXTDM_X3_NO_TILE"); return v && v[0] && v[0] != '0'; }();
-  static const bool only16 = [] { const char* v = getenv("EXTDM_X3_TILE1_16"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_X3_NO_TILE");
+  static const bool only16 = env_flag("EXTDM_X3_TILE1_16");
   const int per = temporal_slots(g);
   return !off && g.mode == 1 && g.D >= 1 && g.D <= 32 && (!only16 || g.D == 16) && (g.H * g.W) % (256 / per) == 0 &&
          groups % 8 == 0 && x.st == (long)x.H * x.W &&
@@ -840,7 +841,7 @@ bool attn_x3_tile1_ok(const View& x, const View& out, const AttnGeom& g, int gro
 // padding, so that a workgroup's 8 windows are one row of windows; 16-B aligned rows;
 // in place (x and out the same view).
 bool attn_x3_tile_ok(const View& x, const View& out, const AttnGeom& g, int groups) {
-  static const bool off = [] { const char* v = getenv("EXTDM_X3_NO_TILE"); return v && v[0] && v[0] != '0'; }();
+  static const bool off = env_flag("EXTDM_X3_NO_TILE");
   return !off && g.mode == 0 && g.ws0 == 2 && g.ws1 == 4 && g.ws2 == 4 && g.W == 32 && g.Wp == 32 && g.H == g.Hp &&
          g.D >= 1 && g.Dp <= g.D + 1 && groups % 8 == 0 && x.p == out.p && x.sc == out.sc && x.sb == out.sb && x.st == out.st &&
          x.st == (long)x.H * x.W && x.sc % 4 == 0 && x.sb % 4 == 0 && ((uintptr_t)x.p & 15) == 0;

@@ -45,6 +45,7 @@
 #include <cstdlib>
 
 #include "attn64_core.h"
+#include "host_util.h"
 
 namespace extdm {
 
@@ -439,8 +440,7 @@ __global__ __launch_bounds__(NW * 64) void temporal64_x3_kernel(const float* x, 
 // The TILE path's geometry (kernel note): whole 4-pixel workgroups inside a sample and 16-B
 // aligned pieces; EXTDM_T64_NO_TILE=1 (read per call) forces the per-lane path (A/B, tests)
 bool t64_tile_ok(const View& x, const View& out, int HW) {
-  const char* v = getenv("EXTDM_T64_NO_TILE");
-  const bool off = v && v[0] && v[0] != '0';
+  const bool off = env_flag("EXTDM_T64_NO_TILE");
   return !off && x.C == 64 && HW % 4 == 0 && x.st % 4 == 0 && x.sc % 4 == 0 && x.sb % 4 == 0 &&
          ((uintptr_t)x.p & 15) == 0 && ((uintptr_t)out.p & 15) == 0;
 }
