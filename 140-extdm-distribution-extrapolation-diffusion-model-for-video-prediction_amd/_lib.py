@@ -16,7 +16,10 @@ EXPORTS = ['extdm_create', 'extdm_destroy', 'extdm_last_error', 'extdm_load_weig
            'extdm_sampler_step_t', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum',
            'extdm_fvd_create', 'extdm_fvd_destroy', 'extdm_fvd_load_weight', 'extdm_fvd_finalize',
            'extdm_fvd_preprocess', 'extdm_fvd_features', 'extdm_fvd_endpoint', 'extdm_fvd_endpoint_shape',
-           'extdm_fvd_range_flag', 'extdm_fvd_same_pad', 'extdm_fvd_maxpool']
+           'extdm_fvd_range_flag', 'extdm_fvd_same_pad', 'extdm_fvd_maxpool',
+           'extdm_lpips_create', 'extdm_lpips_destroy', 'extdm_lpips_load_weight', 'extdm_lpips_finalize',
+           'extdm_lpips_distance', 'extdm_lpips_features', 'extdm_lpips_feature_shape', 'extdm_lpips_maxpool',
+           'extdm_lpips_mean_weights', 'extdm_lpips_range_flag']
 # ... and the declared symbols whose names hold a digit: tests/test_abi.py scans the header for
 # lower-case names only, so they are listed apart (tests/test_teacher_cpu.py checks them)
 EXPORTS_DIGIT = ['extdm_x0_loss']
@@ -151,6 +154,26 @@ def load():
     L.extdm_fvd_same_pad.restype = i32
     L.extdm_fvd_maxpool.argtypes = [vp] + [i32] * 11 + [vp, vp]
     L.extdm_fvd_maxpool.restype = i32
+    L.extdm_lpips_create.argtypes = [i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.extdm_lpips_create.restype = i32
+    L.extdm_lpips_destroy.argtypes = [vp]
+    L.extdm_lpips_destroy.restype = None
+    L.extdm_lpips_load_weight.argtypes = [vp, ctypes.c_char_p, vp, i32, ctypes.POINTER(i64), i32]
+    L.extdm_lpips_load_weight.restype = i32
+    L.extdm_lpips_finalize.argtypes = [vp]
+    L.extdm_lpips_finalize.restype = i32
+    L.extdm_lpips_distance.argtypes = [vp, i32, i32, i32, i32, vp, lg, lg, vp, lg, lg, i32, vp, vp, vp]
+    L.extdm_lpips_distance.restype = i32
+    L.extdm_lpips_features.argtypes = [vp, i32, i32, i32, i32, vp, lg, lg, i32, i32, vp, vp]
+    L.extdm_lpips_features.restype = i32
+    L.extdm_lpips_feature_shape.argtypes = [i32, i32, i32, ctypes.POINTER(i32)]
+    L.extdm_lpips_feature_shape.restype = i32
+    L.extdm_lpips_maxpool.argtypes = [vp, i32, i32, i32, i32, vp, vp]
+    L.extdm_lpips_maxpool.restype = i32
+    L.extdm_lpips_mean_weights.argtypes = [i32, i32, ctypes.POINTER(ctypes.c_double)]
+    L.extdm_lpips_mean_weights.restype = i32
+    L.extdm_lpips_range_flag.argtypes = [vp, i32, vp]
+    L.extdm_lpips_range_flag.restype = i32
     _lib = L
     return L
 
@@ -510,6 +533,106 @@ class FvdHandle:
 
     def range_flag(self, reset=True):
         rc = load().extdm_fvd_range_flag(self.h, 1 if reset else 0, _stream())
+        if rc < 0:
+            check(rc)
+        return rc
+
+
+LPIPS_NORMALIZE, LPIPS_TRANS, LPIPS_PLAIN_MEAN = 1, 2, 4  # include/extdm.h EXTDM_LPIPS_*
+LPIPS_TAPS = ('relu1', 'relu2', 'relu3', 'relu4', 'relu5')
+
+
+def lpips_mean_weights(n_in, n_out):
+    """extdm_lpips_mean_weights: float64 numpy [n_in], the column means of the bilinear
+    (align_corners=False) interpolation matrix from n_in to n_out samples. No device needed."""
+    import numpy as np
+    w = (ctypes.c_double * n_in)()
+    if load().extdm_lpips_mean_weights(n_in, n_out, w) != 0:
+        raise ValueError('lpips_mean_weights: positive sizes expected')
+    return np.array(w[:], dtype=np.float64)
+
+
+def lpips_feature_shape(H, W, tap):
+    """(C, h, w) of tap 0 .. 4 = relu1 .. relu5 for an H x W input (extdm_lpips_feature_shape)."""
+    d = (ctypes.c_int * 3)()
+    check(load().extdm_lpips_feature_shape(H, W, tap, d))
+    return tuple(d)
+
+
+def lpips_maxpool(x):
+    """nn.MaxPool2d(3, 2) of a contiguous fp32 device [B, C, H, W] (extdm_lpips_maxpool)."""
+    import torch
+    _require_device(x)
+    B, C, H, W = x.shape
+    out = torch.empty(B, C, (H - 3) // 2 + 1, (W - 3) // 2 + 1, device=x.device, dtype=torch.float32)
+    with torch.cuda.device(x.device):
+        check(load().extdm_lpips_maxpool(_ptr(x), B, C, H, W, _ptr(out), _stream()))
+    return out
+
+
+def _lpips_images(*ts):
+    """fp32 device [N, C, H, W] image sets with contiguous planes (batch / channel strides free)."""
+    import torch
+    for x in ts:
+        if not x.is_cuda:
+            raise RuntimeError('ExtDM HIP path needs tensors on a ROCm device (no CPU fallback)')
+        if x.dim() != 4 or x.dtype != torch.float32 or x.stride(-1) != 1 or x.stride(-2) != x.shape[-1] or \
+                x.stride(0) < 0 or x.stride(1) < 0:
+            raise ValueError('lpips: fp32 [N, C, H, W] with contiguous planes expected')
+        if x.shape[1] not in (1, 3):
+            raise ValueError('lpips: 1 or 3 channels expected')
+        if x.shape[2] < 31 or x.shape[3] < 31:
+            raise ValueError(f'lpips: H and W must be at least 31, got {x.shape[2]} x {x.shape[3]}')
+
+
+class LpipsHandle:
+    """One native LPIPS (AlexNet, version 0.1) instance (include/extdm.h, extdm_lpips_*)."""
+
+    def __init__(self, max_pairs, max_h, max_w, device=0):
+        h = ctypes.c_void_p()
+        check(load().extdm_lpips_create(max_pairs, max_h, max_w, device, ctypes.byref(h)))
+        self.h = h
+        self.max_pairs, self.max_h, self.max_w = max_pairs, max_h, max_w
+
+    def __del__(self):
+        if getattr(self, 'h', None) and _lib is not None:
+            _lib.extdm_lpips_destroy(self.h)
+            self.h = None
+
+    def load_state(self, sd):
+        """sd: the package's state_dict key -> tensor."""
+        import torch
+        L = load()
+        for name, t in sd.items():
+            t = t.detach().to('cpu').contiguous().to(torch.float32)
+            shape = (ctypes.c_int64 * max(1, t.dim()))(*t.shape)
+            check(L.extdm_lpips_load_weight(self.h, name.encode(), ctypes.c_void_p(t.data_ptr()), 0, shape, t.dim()))
+
+    def finalize(self):
+        check(load().extdm_lpips_finalize(self.h))
+
+    def distance(self, in0, in1, flags=0, mean=None, map=None):
+        """in0, in1 [N, C, H, W]; mean [N] and / or map [N, H, W], contiguous fp32 device tensors."""
+        _lpips_images(in0, in1)
+        _require_device(mean, map)
+        if in0.shape != in1.shape:
+            raise ValueError('lpips: the two image sets must have the same shape')
+        N, C, H, W = in0.shape
+        check(load().extdm_lpips_distance(self.h, N, C, H, W, _ptr(in0), in0.stride(0), in0.stride(1), _ptr(in1),
+                                          in1.stride(0), in1.stride(1), flags, _ptr(mean), _ptr(map), _stream()))
+
+    def features(self, x, tap, flags=0):
+        """Tap 0 .. 4 = relu1 .. relu5 of x [N, C, H, W] -> a new [N, C', h, w] tensor."""
+        import torch
+        _lpips_images(x)
+        N, C, H, W = x.shape
+        out = torch.empty(N, *lpips_feature_shape(H, W, tap), device=x.device, dtype=torch.float32)
+        check(load().extdm_lpips_features(self.h, N, C, H, W, _ptr(x), x.stride(0), x.stride(1), flags, tap,
+                                          _ptr(out), _stream()))
+        return out
+
+    def range_flag(self, reset=True):
+        rc = load().extdm_lpips_range_flag(self.h, 1 if reset else 0, _stream())
         if rc < 0:
             check(rc)
         return rc

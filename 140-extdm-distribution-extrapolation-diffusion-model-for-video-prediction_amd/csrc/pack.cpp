@@ -101,6 +101,22 @@ Frags pack_unit3d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int s
   });
 }
 
+Frags pack_conv2d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int stem_row) {
+  const int KK = KS * KS, K = stem_row ? KS * stem_row : KK * Cpad;
+  return pack_frags(1, M, K, bm, [&](int, int m, int k, float& v) {
+    int tap = k / Cpad, ci = k - tap * Cpad;
+    if (stem_row) {
+      const int ky = k / stem_row, j = k - ky * stem_row;
+      if (j >= KS * Cin) return false;
+      tap = ky * KS + j / Cin;
+      ci = j % Cin;
+    }
+    if (ci >= Cin) return false;
+    v = w[((size_t)m * Cin + ci) * KK + tap];
+    return true;
+  });
+}
+
 Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng) {
   const int kk = ks * ks, cib = 16 * ng, ncgb = (ci + cib - 1) / cib, mt = (co + bm - 1) / bm;
   const int m32 = bm / 32, steps = ng * ks;

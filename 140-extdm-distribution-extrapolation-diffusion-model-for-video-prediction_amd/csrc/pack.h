@@ -1,6 +1,7 @@
 // Weight layouts of the MFMA / VALU kernels as pure host functions (no HIP, no kernels.h): host
-// vectors and the tile parameters the kernel files choose in, host vectors out. runtime.cpp and
-// fvd.cpp upload the results; tests/pack_driver.cpp runs the same functions on the CPU.
+// vectors and the tile parameters the kernel files choose in, host vectors out. runtime.cpp,
+// fvd.cpp and lpips.cpp upload the results; tests/pack_driver.cpp and tests/pack_lpips_driver.cpp
+// run the same functions on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -73,6 +74,11 @@ Frags pack_gemm_x3(const GemmPlane& p, int npar, int M, int K, int bm, int kk);
 // past Cin absent). stem_row > 0: the 3-channel stem's (kt, ky) rows of 7 kx * 3 ci = 21 elements
 // padded to stem_row, K = KS*KS*stem_row (i3d.hip STEM)
 Frags pack_unit3d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int stem_row);
+// Conv2d weight [M][Cin][KS][KS] for conv2d_x3_kernel (lpips.hip): pack_frags with k = (ky * KS +
+// kx) * Cpad + ci (channels past Cin absent). stem_row > 0: the 3-channel stem's ky rows of
+// KS kx * Cin ci elements (j = kx * Cin + ci) padded to stem_row, k = ky * stem_row + j,
+// K = KS * stem_row (AlexNet's 11x11: 33 of 40, K = 440)
+Frags pack_conv2d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int stem_row);
 // f16x3 layout (conv_x3.hip): [mtile][cb*KS + ky][(g, kx)][m32][hi|lo][lane][8], lane = (h, lc): row
 // m = mtile*BM + m32*32 + lc, input channel cb*16NG + g*16 + 8h + e. Rows scaled as in pack_frags.
 Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng);

@@ -11,7 +11,9 @@ from `InceptionI3d` (metrics/pytorch_i3d.py, on the native library's 3-D convolu
 the mirrored front end of metrics/calculate_fvd.py and fvd.py (`trans`, `preprocess_single`,
 `get_fvd_feats`, `get_feats`, `calculate_fvd*`); the weights are the user's own
 i3d_pretrained_400.pt state_dict (`load_i3d_pretrained`), which the reference does not ship
-either. LPIPS needs a network and a package that are absent: not computed.
+either. LPIPS (metrics/calculate_lpips.py) is `LPIPS`, the published package's AlexNet metric
+restated on the native library's 2-D convolution and distance head, with the user's own weight
+files (`load_lpips_pretrained`); all frame pairs of a call run as one batch.
 """
 import numpy as np
 import torch
@@ -159,7 +161,7 @@ def metric_stuff(metric):
 
 
 def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, result_feats=None, i3d=None,
-                 mini_bs=16):
+                 mini_bs=16, lpips=None):
     """The metric half of valid.py:199-257 on [b, n, t, c, h, w] videos: per clip the best of
     its n samples for PSNR and SSIM over the predicted frames (calculate_psnr2 /
     calculate_ssim2), summarised by metric_stuff. With video features (origin [b, d], result
@@ -171,8 +173,10 @@ def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, r
     origin_videos[:, 0] and result_feats from the `(b n)` flattening (valid.py:203-204), in
     mini-batches of mini_bs. The reference runs the detector again on the selected videos
     (valid.py:235); here their rows of result_feats are taken, which is the same thing because
-    a video's features do not depend on its batch. LPIPS needs network weights the reference
-    does not ship: not computed."""
+    a video's features do not depend on its batch. With `lpips` (an LPIPS with the user's
+    weights, load_lpips_pretrained) the best sample per clip by LPIPS over the predicted frames
+    (calculate_lpips2, valid.py:228) summarised by metric_stuff as 'lpips' / '_std' / '_conf95'
+    (valid.py:243); without it the dict has no LPIPS entries."""
     if i3d is not None and origin_feats is None and result_feats is None:
         origin_feats = get_feats(origin_videos[:, 0], origin_videos.device, mini_bs=mini_bs, i3d=i3d)
         result_feats = get_feats(result_videos.flatten(0, 1), result_videos.device, mini_bs=mini_bs, i3d=i3d)
@@ -191,6 +195,9 @@ def eval_metrics(origin_videos, result_videos, cond_frames, origin_feats=None, r
         # per trajectory: the features of every clip's traj-th sample (valid.py:207-209)
         fvd_list = [frechet_distance(np.asarray(origin_feats), rf[:, traj]) for traj in range(n)]
         out['fvd_traj_mean'], out['fvd_traj_std'], out['fvd_traj_conf95'] = metric_stuff(np.array(fvd_list))
+    if lpips is not None:
+        lpips_list = best_of_n_lpips(origin_videos, result_videos, cond_frames, lpips)
+        out['lpips'], out['lpips_std'], out['lpips_conf95'] = metric_stuff(np.array(lpips_list))
     return out
 
 
@@ -421,3 +428,244 @@ def calculate_fvd1(videos1, videos2, device, mini_bs=10, i3d=None):
 def calculate_fvd2(feats1, feats2):
     """calculate_fvd.py:76-77."""
     return frechet_distance(feats1, feats2)
+
+
+# ---------------------------------------------------------------- LPIPS (AlexNet, version 0.1)
+_LPIPS_CONVS = (('slice1', 0, 3, 64, 11, 4, 2), ('slice2', 3, 64, 192, 5, 1, 2), ('slice3', 6, 192, 384, 3, 1, 1),
+                ('slice4', 8, 384, 256, 3, 1, 1), ('slice5', 10, 256, 256, 3, 1, 1))
+
+
+class _ScalingLayer(nn.Module):
+    """lpips.ScalingLayer: the two buffers of (inp - shift) / scale."""
+
+    def __init__(self):
+        super().__init__()
+        self.register_buffer('shift', torch.Tensor([-.030, -.088, -.188])[None, :, None, None])
+        self.register_buffer('scale', torch.Tensor([.458, .448, .450])[None, :, None, None])
+
+
+class _AlexSlices(nn.Module):
+    """Parameter holder of lpips.pretrained_networks.alexnet: the five convs under torchvision's
+    `features` indices (the ReLUs and pools between them have no state)."""
+
+    def __init__(self):
+        super().__init__()
+        for name, idx, cin, cout, k, s, p in _LPIPS_CONVS:
+            seq = nn.Sequential()
+            seq.add_module(str(idx), nn.Conv2d(cin, cout, k, stride=s, padding=p))
+            self.add_module(name, seq)
+
+
+class _NetLinLayer(nn.Module):
+    """lpips.NetLinLayer: Dropout (identity at inference) + Conv2d(chn_in, 1, 1, bias=False)."""
+
+    def __init__(self, chn_in):
+        super().__init__()
+        self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn_in, 1, 1, stride=1, padding=0, bias=False))
+
+
+class LPIPS(nn.Module):
+    """lpips.LPIPS(net='alex', version='0.1', lpips=True), the metric of
+    metrics/calculate_lpips.py:12, on the native library. The `lpips` package is not part of the
+    reference, so the network is restated from the published package: the package's
+    constructor signature, its 22 state_dict entries (`scaling_layer.*`, `net.sliceK.N.*`,
+    `linK.model.1.weight` and the `lins.K` aliases sharing storage), forward(in0, in1,
+    retPerLayer=False, normalize=False) -> [N, 1, H, W] with spatial=True, [N, 1, 1, 1] without.
+    `pretrained=True` loads nothing (there is no file to load): weights come from load_state_dict
+    or load_lpips_pretrained. Inference only; inputs are [N, 1 or 3, H >= 31, W >= 31] device
+    tensors in [-1, 1] ([0, 1] with normalize=True). A pair's value is bitwise independent of the
+    batch it sits in."""
+
+    def __init__(self, pretrained=True, net='alex', version='0.1', lpips=True, spatial=False, pnet_rand=False,
+                 pnet_tune=False, use_dropout=True, model_path=None, eval_mode=True, verbose=True):
+        if net not in ('alex', 'alexnet'):
+            raise NotImplementedError(f"LPIPS: only net='alex' is built, got {net!r}")
+        if not lpips:
+            raise NotImplementedError('LPIPS: lpips=False (unweighted feature distance) is not built')
+        if version != '0.1':
+            raise NotImplementedError(f"LPIPS: only version='0.1' (with the scaling layer) is built, got {version!r}")
+        if not use_dropout:
+            raise NotImplementedError('LPIPS: use_dropout=False changes the lin keys and is not built')
+        super().__init__()
+        self.pnet_type, self.pnet_tune, self.pnet_rand = 'alex', pnet_tune, pnet_rand
+        self.spatial, self.lpips, self.version = spatial, lpips, version
+        self.chns = [c[3] for c in _LPIPS_CONVS]
+        self.L = len(self.chns)
+        self.scaling_layer = _ScalingLayer()
+        self.net = _AlexSlices()
+        for k, c in enumerate(self.chns):
+            setattr(self, f'lin{k}', _NetLinLayer(c))
+        self.lins = nn.ModuleList([getattr(self, f'lin{k}') for k in range(self.L)])
+        if model_path is not None:
+            self.load_state_dict(torch.load(model_path, map_location='cpu'), strict=False)
+        self.eval()
+        self.chunk = 1024  # pairs per native launch sequence
+        self._handle = None
+
+    def _state_version(self):
+        return tuple((p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
+
+    def _h(self, device, N, H, W):
+        """Native handle holding N pairs of H x W, rebuilt when the state changes or it is too small."""
+        dev = device.index or 0
+        h = self._handle
+        ver = self._state_version()
+        if h is None or h[0] != dev or h[1] < N or h[2] < H or h[3] < W or h[4] != ver:
+            same = h is not None and h[0] == dev
+            N2, H2, W2 = max(N, h[1] if same else 0), max(H, h[2] if same else 0), max(W, h[3] if same else 0)
+            self._handle = None  # frees the old workspace first
+            nh = _lib.LpipsHandle(N2, H2, W2, dev)
+            nh.load_state(self.state_dict())
+            nh.finalize()
+            self._handle = h = (dev, N2, H2, W2, ver, nh)
+        return h[5]
+
+    @staticmethod
+    def _images(x):
+        _need_rocm(x)
+        if x.dim() != 4:
+            raise ValueError(f'LPIPS: [N, C, H, W] expected, got {tuple(x.shape)}')
+        if x.dtype != torch.float32 or x.stride(-1) != 1 or x.stride(-2) != x.shape[-1] or x.stride(0) < 0 or \
+                x.stride(1) < 0:
+            x = x.float().contiguous()
+        return x
+
+    @torch.no_grad()
+    def distance(self, in0, in1, flags=0, want_map=False, want_mean=True):
+        """(mean [N] or None, map [N, H, W] or None) of N pairs, in chunks of self.chunk pairs."""
+        in0, in1 = self._images(in0), self._images(in1)
+        if in0.shape != in1.shape:
+            raise ValueError('LPIPS: the two image sets must have the same shape')
+        N, _, H, W = in0.shape
+        _lib._lpips_images(in0, in1)
+        mean = torch.empty(N, device=in0.device) if want_mean else None
+        smap = torch.empty(N, H, W, device=in0.device) if want_map else None
+        step = max(1, int(self.chunk))
+        h = self._h(in0.device, min(N, step), H, W)
+        with torch.cuda.device(in0.device):
+            for i in range(0, N, step):
+                j = min(N, i + step)
+                h.distance(in0[i:j], in1[i:j], flags, mean[i:j] if want_mean else None,
+                           smap[i:j] if want_map else None)
+        return mean, smap
+
+    def forward(self, in0, in1, retPerLayer=False, normalize=False):
+        if retPerLayer:
+            raise NotImplementedError('LPIPS: retPerLayer=True is not built')
+        flags = _lib.LPIPS_NORMALIZE if normalize else 0
+        if self.spatial:
+            return self.distance(in0, in1, flags, want_map=True, want_mean=False)[1][:, None]
+        return self.distance(in0, in1, flags | _lib.LPIPS_PLAIN_MEAN)[0][:, None, None, None]
+
+    @torch.no_grad()
+    def features(self, x, tap, normalize=False):
+        """Tap 'relu1' .. 'relu5' (or 0 .. 4) of one image set, post-ReLU and un-normalised: the
+        parity hook."""
+        x = self._images(x)
+        _lib._lpips_images(x)
+        k = _lib.LPIPS_TAPS.index(tap) if isinstance(tap, str) else int(tap)
+        N, _, H, W = x.shape
+        h = self._h(x.device, (N + 1) // 2, H, W)
+        with torch.cuda.device(x.device):
+            return h.features(x, k, _lib.LPIPS_NORMALIZE if normalize else 0)
+
+
+def load_lpips_pretrained(device, alexnet_path, lin_path):
+    """LPIPS with the two files users have: torchvision's AlexNet state_dict (`features.N.weight`
+    -> `net.sliceK.N.weight`) and the package's alex.pth (`linK.model.1.weight`). Nothing is ever
+    fetched."""
+    import os
+    for path, what in ((alexnet_path, "torchvision's AlexNet state_dict"), (lin_path, "the lpips package's alex.pth")):
+        if not os.path.exists(path):
+            raise FileNotFoundError(f'LPIPS weights not found: {path} ({what})')
+    net = LPIPS(pretrained=False)
+    alex = torch.load(alexnet_path, map_location='cpu')
+    sd = {}
+    for name, idx, *_ in _LPIPS_CONVS:
+        for s in ('weight', 'bias'):
+            key = f'features.{idx}.{s}'
+            if key not in alex:
+                raise KeyError(f'{alexnet_path}: missing {key}')
+            sd[f'net.{name}.{idx}.{s}'] = alex[key]
+    lin = torch.load(lin_path, map_location='cpu')
+    for k in range(5):
+        key = f'lin{k}.model.1.weight'
+        if key not in lin:
+            raise KeyError(f'{lin_path}: missing {key}')
+        sd[key] = lin[key]
+    missing, unexpected = net.load_state_dict(sd, strict=False)
+    assert not unexpected and all(m.startswith(('lins.', 'scaling_layer.')) for m in missing), (missing, unexpected)
+    return net.to(device).eval()
+
+
+def lpips_trans(x):
+    """calculate_lpips.py:15-23: grey -> 3 channels, [0, 1] -> [-1, 1]. The calculate_lpips*
+    functions below do this inside the native stem (EXTDM_LPIPS_TRANS) instead."""
+    if x.shape[-3] == 1:
+        x = x.repeat(1, 1, 3, 1, 1)
+    return x * 2 - 1
+
+
+def _need_lpips(loss_fn):
+    if loss_fn is None:
+        raise ValueError('LPIPS needs a network with weights: pass loss_fn=LPIPS(...) (load_lpips_pretrained)')
+    return loss_fn
+
+
+def lpips_frames(videos1, videos2, device, loss_fn=None):
+    """`loss_fn.forward(img1, img2).mean()` of every frame pair of two [b, t, c, h, w] videos in
+    [0, 1] (the loops of calculate_lpips.py:40-60): float64 numpy [b, t]. All b * t pairs run
+    through the native handle as one batch, in chunks."""
+    loss_fn = _need_lpips(loss_fn)
+    assert videos1.shape == videos2.shape  # calculate_lpips.py:29
+    if videos1.dim() != 5:
+        raise ValueError('expected [b, t, c, h, w] videos')
+    b, t = videos1.shape[:2]
+    v1, v2 = videos1.to(device).flatten(0, 1), videos2.to(device).flatten(0, 1)
+    flags = _lib.LPIPS_TRANS | (0 if loss_fn.spatial else _lib.LPIPS_PLAIN_MEAN)
+    mean = loss_fn.distance(v1, v2, flags)[0]
+    return mean.double().cpu().numpy().reshape(b, t)
+
+
+def calculate_lpips(videos1, videos2, device, loss_fn=None):
+    """metrics/calculate_lpips.py:25-76: mean / std over videos per frame index. The reference
+    indexes its list of lists with [:, t] (line 66) and raises TypeError; this is the evident
+    np.array form (DESIGN, reference defects)."""
+    v = lpips_frames(videos1, videos2, device, loss_fn)
+    shape = list(videos1.shape[2:])
+    if shape[0] == 1:
+        shape[0] = 3  # the reference reports the shape after trans
+    return {'lpips': {f'avg[{i}]': np.mean(v[:, i]) for i in range(v.shape[1])},
+            'lpips_std': {f'std[{i}]': np.std(v[:, i]) for i in range(v.shape[1])},
+            'lpips_video_setting': torch.Size([videos1.shape[1]] + shape),
+            'lpips_video_setting_name': 'time, channel, heigth, width'}
+
+
+def calculate_lpips1(videos1, videos2, device, loss_fn=None):
+    """metrics/calculate_lpips.py:78-95: (mean, std) over every frame."""
+    v = lpips_frames(videos1, videos2, device, loss_fn)
+    return np.mean(v), np.std(v)
+
+
+def calculate_lpips2(videos1, videos2, device, loss_fn=None):
+    """metrics/calculate_lpips.py:97-115: the best of the n samples, min over n of the per-sample
+    mean over frames."""
+    v = lpips_frames(videos1, videos2, device, loss_fn)
+    return np.min(np.mean(v, axis=-1))
+
+
+def calculate_lpips3(videos1, videos2, device, loss_fn=None):
+    """metrics/calculate_lpips.py:117-135: the per-video mean over frames."""
+    v = lpips_frames(videos1, videos2, device, loss_fn)
+    return np.mean(v, axis=-1)
+
+
+def best_of_n_lpips(origin_videos, result_videos, cond_frames, loss_fn):
+    """valid.py:222-228: calculate_lpips2 of each clip's n samples over the predicted frames.
+    origin_videos, result_videos: [b, n, t, c, h, w]. One value per clip; all b * n * t pairs go
+    through the handle as one batch (a pair's value does not depend on its batch)."""
+    b, n = result_videos.shape[:2]
+    a = origin_videos[:, :, cond_frames:].flatten(0, 1)
+    r = result_videos[:, :, cond_frames:].flatten(0, 1)
+    v = lpips_frames(a, r, result_videos.device, loss_fn).reshape(b, n, -1)
+    return [np.min(np.mean(v[i], axis=-1)) for i in range(b)]

@@ -335,6 +335,62 @@ int extdm_fvd_same_pad(int size, int kernel, int stride, int* front, int* back);
 /* 1 if a convolution input of this handle reached |v| >= 65504 since the last reset. */
 int extdm_fvd_range_flag(ExtdmFvdHandle* h, int reset, void* stream);
 
+/* ---- LPIPS: lpips.LPIPS(net='alex', version='0.1') on a handle of its own ----
+ * The metric of metrics/calculate_lpips.py:12. The `lpips` package is not part of the reference, so
+ * the network is restated from the published package: ScalingLayer.forward, the five ReLU taps of
+ * pretrained_networks.alexnet.forward, normalize_tensor, NetLinLayer, upsample / spatial_average and
+ * the sum of LPIPS.forward. Weights go in under the package's state_dict keys: `scaling_layer.shift`
+ * / `.scale` [1][3][1][1], `net.slice1.0`, `net.slice2.3`, `net.slice3.6`, `net.slice4.8`,
+ * `net.slice5.10` with `.weight` / `.bias`, and `linK.model.1.weight` [1][C_K][1][1], K = 0 .. 4;
+ * `lins.K.model.1.weight` is accepted as an alias of `linK...` and must equal it if both are given.
+ * extdm_lpips_finalize packs the convs for the f16x3 2-D convolution and allocates the workspace for
+ * max_pairs pairs of max_h x max_w images; a missing key is an error naming the key. */
+typedef struct ExtdmLpipsHandle ExtdmLpipsHandle;
+int extdm_lpips_create(int max_pairs, int max_h, int max_w, int device, ExtdmLpipsHandle** out);
+void extdm_lpips_destroy(ExtdmLpipsHandle* h);
+int extdm_lpips_load_weight(ExtdmLpipsHandle* h, const char* name, const void* host_ptr, int dtype,
+                            const int64_t* shape, int ndim);
+int extdm_lpips_finalize(ExtdmLpipsHandle* h);
+
+/* flags of extdm_lpips_distance / extdm_lpips_features */
+#define EXTDM_LPIPS_NORMALIZE 1  /* LPIPS.forward(normalize=True): x * 2 - 1 first */
+#define EXTDM_LPIPS_TRANS 2      /* trans (calculate_lpips.py:15-23): x * 2 - 1 first */
+#define EXTDM_LPIPS_PLAIN_MEAN 4 /* mean_out as LPIPS(spatial=False): spatial_average of each lin map */
+
+/* LPIPS.forward(in0, in1) for N pairs in one batch (replaces the one-pair-per-forward loops of
+ * calculate_lpips.py:40-60, 83-93, 102-112, 122-132): in0, in1 [N][C][H][W] through the element
+ * strides sn / sc (planes contiguous H*W), C = 1 replicated to 3 (trans, calculate_lpips.py:17-18).
+ * mean_out [N]: the mean of the spatial map (calculate_lpips.py:59 `.mean()`), computed from the
+ * small lin maps as sum_ij wy[i] wx[j] m[i][j] (extdm_lpips_mean_weights) in fp64; with
+ * EXTDM_LPIPS_PLAIN_MEAN the spatial=False value instead. map_out [N][H][W]: the spatial=True map
+ * (bilinear upsample, align_corners=False, of the five lin maps, summed). Either may be NULL. Errors
+ * on H or W < 31 (the second MaxPool2d(3, 2) has no output), N > max_pairs, H > max_h or W > max_w.
+ * A pair's values do not depend on the batch it sits in. Fails if an f16x3 convolution input
+ * reached |v| >= 65504 (the sticky range flag, reset at entry). Synchronises the stream. */
+int extdm_lpips_distance(ExtdmLpipsHandle* h, int N, int C, int H, int W, const float* in0, long sn0, long sc0,
+                         const float* in1, long sn1, long sc1, int flags, float* mean_out, float* map_out,
+                         void* stream);
+
+/* The parity hook: tap 0 .. 4 = relu1 .. relu5 of pretrained_networks.alexnet.forward for one image
+ * set x [N][C][H][W] (N <= 2 max_pairs), post-ReLU and un-normalised, into out [N][C'][h][w];
+ * extdm_lpips_feature_shape writes dims = {C', h, w} (no device needed; 0 extents where the input
+ * is too small). */
+int extdm_lpips_features(ExtdmLpipsHandle* h, int N, int C, int H, int W, const float* x, long sn, long sc, int flags,
+                         int tap, float* out, void* stream);
+int extdm_lpips_feature_shape(int H, int W, int tap, int* dims);
+
+/* nn.MaxPool2d(kernel_size=3, stride=2) (torchvision alexnet features 2 and 5) of a contiguous x
+ * [B][C][H][W] into out [B][C][(H-3)/2+1][(W-3)/2+1]. Not tied to a handle. */
+int extdm_lpips_maxpool(const float* x, int B, int C, int H, int W, float* out, void* stream);
+
+/* The separable weights of the mean of an upsampled map (lpips.upsample + calculate_lpips.py:59):
+ * w[i], i < in, the column means of the 1-D bilinear (align_corners=False) interpolation matrix
+ * from `in` to `out` samples, in fp64; they sum to 1. A host function, no device. -1: bad argument. */
+int extdm_lpips_mean_weights(int in, int out, double* w);
+
+/* 1 if a convolution input of this handle reached |v| >= 65504 since the last reset. */
+int extdm_lpips_range_flag(ExtdmLpipsHandle* h, int reset, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
