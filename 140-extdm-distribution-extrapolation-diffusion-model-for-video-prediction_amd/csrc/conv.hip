@@ -248,6 +248,7 @@ int conv_forward(hipStream_t s, const View& out, const View& in0, const View* in
   if (epi_in.res_aff) throw std::invalid_argument("conv: residual GroupNorm needs the f16x3 direct conv");
   ConvEpi epi = epi_in;  // the other paths leave the statistics to the caller
   epi.stats = nullptr;
+  if (w.tx && conv_x3_updown_forward(s, out, in0, in1, w, stride, pad, epi)) return 0;
   if (conv_gemm_x3_forward(s, out, in0, in1, w, stride, pad, epi)) return 0;
   if (w.mode == MODE_CONV && stride == 1 && w.KH == w.KW && pad == w.KH / 2 && !halo_off() &&
       conv_halo_forward(s, out, in0, in1, w, epi))

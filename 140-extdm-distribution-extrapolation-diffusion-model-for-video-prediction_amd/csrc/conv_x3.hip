@@ -5,7 +5,8 @@
 // with every product exact in the fp32 accumulator (11 x 11 significant bits).
 // The dropped a_lo*b_lo term and the representation error of hi + lo are
 // ~2^-22 relative, below fp32 accumulation error at these K (K = Cin*k*k up to
-// 25 088); the Unet eps matches the fp64 evaluation as closely as the fp32
+// 25 088; the stride-2 (1,4,4) convs of the U-Net run on the same tiles as sums of 2x2-tap
+// stride-1 convs: kernel note TT, conv_x3_updown_forward); the Unet eps matches the fp64 evaluation as closely as the fp32
 // CPU reference does (tests/test_gpu_parity.py). Weights are
 // pre-scaled per output channel by a power of two (exact) so their lo parts stay
 // normal in fp16; activations must satisfy |v| < 65504, which the staging checks
@@ -78,6 +79,7 @@ struct X3Args {
   // m-tile-0 workgroups while staging (fea_x3.hip reads them); null: not written
   float* edge;
   int mfast;
+  int mtc;  // TT = 1: m-tiles per output phase
   int in0_bytes, in1_bytes;  // BUFX: byte extents of the two sources (< 2^30), 0 = not usable
   ConvEpi e;
 };
@@ -172,18 +174,29 @@ template <> struct XMaxX3<5, 256> { static constexpr int v = 400; };
 // runtime choice both staging paths shared the channel-block loop, and merging them cost the loop
 // register copies and 64-bit address arithmetic on the path taken (static count of the level-0
 // 3x3 tile's loop: 1192 VALU + 521 SALU per 108 MFMAs; 249 + 218 with BX).
+// TT: two-tap mode, the stride-2 (1,4,4)/p1 convs on the KS = 3 halo geometry (PAD 1, RS = W + 2,
+// TH + 2 rows): the (ky, kx) loops and the packed slice [ky'][kx'] cover the 2x2 taps from a tap
+// origin (oy, ox) inside the 3x3 window, two stages per channel block (pack.h, two-tap layouts).
+// 1 = ConvTranspose: the m-tile is (output phase (py, px), channel tile ct), origin (py, px), tile
+// pixel (row, col) stored at (2 row + py, 2 col + px) of the 2H x 2W output. 2 = Downsample: the
+// channel-block loop runs over (input phase q = (qy, qx), 16-channel block) in that order, block
+// (q, cb) stages the phase plane in[2 iy + qy][2 ix + qx] (the phase's qy Win + qx in the buffer
+// loads' scalar offset; a position is inside the image independently of the phase) and reads it
+// from origin (1 - qy, 1 - qx). BX staging only.
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF, bool SPAN, int NS, bool XOP = false,
-          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false>
+          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false, int TT = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 && KS == 5 ? 2 : 1))) void conv_x3_kernel(X3Args a) {
   constexpr int NT = NW * 64;
   constexpr int PAD = KS / 2;
   constexpr int CIB = 16 * NG;
   constexpr int MT32 = BM / 32;
-  constexpr int STEPS = NG * KS;                // per A slot: (g, kx)
+  constexpr int KT = TT ? 2 : KS;               // taps per axis
+  constexpr int STEPS = NG * KT;                // per A slot: (g, kx)
   constexpr int AH = STEPS * MT32 * 2 * 512;    // halves per ky slice
   constexpr int AHS = KY * AH;                  // halves per A slot (stage)
-  constexpr int STG = KS / KY;                  // stages per channel block
-  static_assert(KS % KY == 0, "KY must divide KS");
+  constexpr int STG = KT / KY;                  // stages per channel block
+  static_assert(KT % KY == 0, "KY must divide the taps");
+  static_assert(!TT || (KS == 3 && NG == 1 && BX && SPAN && !XOP && !WS && !PH && SPL == 0), "TT: staged 3x3 geometry");
   constexpr int NSLOT = NS;
   constexpr int WM = NW / WN;
   constexpr int TM = BM / (32 * WM);
@@ -223,9 +236,12 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   // MFAST (1x1 with all m-tiles' weights within an XCD's L2, host: x3_mfast): the k-th
   // workgroup of XCD x takes m-tile k % MT of pixel tile x + 8 (k / MT), so a pixel tile's MT
   // m-tiles run back to back on one XCD and its input is read from HBM once (the default
-  // order re-read it once per m-tile: the ups.3 Tmodulator 7 x 235 MB)
+  // order re-read it once per m-tile: the ups.3 Tmodulator 7 x 235 MB). TT = 1 takes the same
+  // order: the m-tiles of a pixel tile are the four output phases, whose stride-2 stores share
+  // every output line, so the lines are completed in that XCD's L2 instead of being written to
+  // HBM in four partial visits a whole grid row apart.
   int tile, mtile;
-  if (KS == 1 && a.mfast) {
+  if ((KS == 1 || TT == 1) && a.mfast) {
     const int lin = (int)(blockIdx.x + gridDim.x * blockIdx.y), MT = (int)gridDim.y;
     const int k = lin >> 3;
     mtile = k % MT;
@@ -244,7 +260,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   const int c0 = SPL == 1 ? (int)blockIdx.z * a.ncgb / a.nsplit : 0;
   const int c1 = SPL == 1 ? ((int)blockIdx.z + 1) * a.ncgb / a.nsplit : a.ncgb;
   const int NIT = c1 * STG;
-  const _Float16* wt = a.w + (long)mtile * a.ncgb * KS * AH;
+  const _Float16* wt = a.w + (long)mtile * a.ncgb * KT * AH;
+  // TT = 1: (phase, channel tile) of this m-tile; row m of the tile is output channel mbase + m
+  const int tph = TT == 1 ? mtile / a.mtc : 0;
+  const int mbase = (TT == 1 ? mtile - tph * a.mtc : mtile) * BM;
+  // TT = 2: input phase of channel block cgb (ncgb = 4 phases x ncgb / 4 blocks)
+  auto in_phase = [&](int cgb) __attribute__((always_inline)) {
+    const int ncb = a.ncgb >> 2;
+    return (cgb >= ncb) + (cgb >= 2 * ncb) + (cgb >= 3 * ncb);
+  };
 
   // ---- staging slots: (group, halo position), 16 channels each ----
   int sg[NSLOT], spos[NSLOT], soff0[NSLOT], soff1[NSLOT];
@@ -262,8 +286,9 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       sg[j] = g; spos[j] = pos;
       if (q < a.P && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) {
         const int b = q / a.T, t = q - b * a.T;
-        soff0[j] = (int)((long)b * a.i0b + (long)t * a.i0t) + iy * a.W + ix;
-        soff1[j] = (int)((long)b * a.i1b + (long)t * a.i1t) + iy * a.W + ix;
+        const int ip = TT == 2 ? 4 * iy * a.W + 2 * ix : iy * a.W + ix;  // TT = 2: phase (0, 0) of the 2H x 2W input
+        soff0[j] = (int)((long)b * a.i0b + (long)t * a.i0t) + ip;
+        soff1[j] = (int)((long)b * a.i1b + (long)t * a.i1t) + ip;
       }
     }
   }
@@ -290,17 +315,20 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     return;
 #endif
     if (bufx) {
+      const int qin = TT == 2 ? in_phase(cgb) : 0;
+      const int cbk = TT == 2 ? cgb - qin * (a.ncgb >> 2) : cgb;
+      const int poff = TT == 2 ? ((qin >> 1) * 2 * a.W + (qin & 1)) * 4 : 0;
 #pragma unroll
       for (int j = 0; j < NSLOT; ++j) {
         // the slot's channel group is wave-uniform (host: one group, or XPOS % 64 == 0)
-        const int ci0 = __builtin_amdgcn_readfirstlane(cgb * CIB + (sg[j] < 0 ? 0 : sg[j]) * 16);
+        const int ci0 = __builtin_amdgcn_readfirstlane(cbk * CIB + (sg[j] < 0 ? 0 : sg[j]) * 16);
         const bool s1 = ci0 >= gC0;
         const int vo = soff0[j] >= 0 ? (s1 ? soff1[j] : soff0[j]) * 4 : 0x40000000;
         const int cb = s1 ? ci0 - gC0 : ci0;
         const int cs4 = (int)(s1 ? gi1c : gi0c) * 4;
 #pragma unroll
         for (int c = 0; c < 16; ++c)
-          xr[j][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s1 ? rsx1 : rsx0, vo, (cb + c) * cs4, 0));
+          xr[j][c] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(s1 ? rsx1 : rsx0, vo, (cb + c) * cs4 + poff, 0));
       }
       return;
     }
@@ -515,6 +543,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     const int r = (n / a.W) % a.TH;
     const int c = n % a.W;
     bpos[j] = (p * THK + r) * a.RS + c;
+    if (TT == 1) bpos[j] += (tph >> 1) * a.RS + (tph & 1);  // tap origin (py, px)
   }
 
   f32x16 acc[TM][TN];
@@ -529,7 +558,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   float* const ep_sc = reinterpret_cast<float*>(xdummy + 32);
   float* const ep_bi = ep_sc + BM;
   if (tid < BM) {
-    const int m = mtile * BM + tid;
+    const int m = mbase + tid;
     const int mc = m < a.Cout ? m : a.Cout - 1;
     ep_sc[tid] = a.wscale[mc];
     ep_bi[tid] = a.e.bias ? a.e.bias[mc] : 0.f;
@@ -618,6 +647,11 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     if (PH && !XOP && kb == 0 && a.edge && mtile == 0) export_edges(Xs, cgb);
     if (it + 1 < NIT) load_a(it + 1, (itr & 1) ? As0 : As1);
     const bool pre = (kb == 0) && more;
+    int torg = 0;  // TT = 2: tap origin (1 - qy, 1 - qx) of this block's phase plane
+    if (TT == 2) {
+      const int qin = in_phase(cgb);
+      torg = (1 - (qin >> 1)) * a.RS + 1 - (qin & 1);
+    }
     if (SPAN) __builtin_amdgcn_sched_barrier(0);  // the X loads issue after the DMA (vmcnt order)
     if (pre) {
       if (XOP) dma_x(cgb + 1, (cr & 1) ? Xs0 : Xs1);
@@ -631,8 +665,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
 #pragma unroll
-      for (int kx = 0; kx < KS; ++kx) {
-        const int step = g * KS + kx;
+      for (int kx = 0; kx < KT; ++kx) {
+        const int step = g * KT + kx;
         h8 ah[TM], al[TM], ad[TM], bh[TN], bl[TN];
 #pragma unroll
         for (int i = 0; i < TM; ++i) {
@@ -643,7 +677,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
-          const int pos = bpos[j] + ky * a.RS + kx;
+          const int pos = bpos[j] + ky * a.RS + kx + torg;
           const _Float16* bp = (XOP || LIN) ? Xs + h * XPL + pos * 8
                                             : Xs + ((long)g * a.XPOS + pos) * 16 + 8 * (h ^ ((pos >> 3) & 1));
           bh[j] = *reinterpret_cast<const h8*>(bp);
@@ -757,7 +791,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     }
 #pragma unroll
     for (int r16 = 0; r16 < 16; ++r16) {
-      const int m = mtile * BM + (wm * TM + i) * 32 + (r16 & 3) + 8 * (r16 >> 2) + 4 * h;
+      const int m = mbase + (wm * TM + i) * 32 + (r16 & 3) + 8 * (r16 >> 2) + 4 * h;
       mrow[r16] = m < a.Cout ? m : a.Cout - 1;
     }
 #pragma unroll
@@ -772,8 +806,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       const int b = q / a.T, t = q - b * a.T;
       // PH: the 64-row block's output phase (BM = 64: the m-tile; BM = 128: two phases of one
       // output row parity, one per wave row)
-      const int ph = (mtile * BM + (wm * TM + i) * 32) / 64;
-      const int pix = PH ? (2 * row + (ph >> 1)) * (2 * a.W) + 2 * c + (ph & 1) : row * a.W + c;
+      const int ph = TT == 1 ? tph : (mtile * BM + (wm * TM + i) * 32) / 64;
+      const int pix = (PH || TT == 1) ? (2 * row + (ph >> 1)) * (2 * a.W) + 2 * c + (ph & 1) : row * a.W + c;
       float v[16];
 #pragma unroll
       for (int r16 = 0; r16 < 16; ++r16) v[r16] = acc[i][j][r16] * scl[r16] + bia[r16];
@@ -815,7 +849,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       const int obase = (int)((long)b * a.ob + (long)t * a.ot) + pix;
 #pragma unroll
       for (int r16 = 0; r16 < 16; ++r16) {
-        const int m = mtile * BM + (wm * TM + i) * 32 + (r16 & 3) + 8 * (r16 >> 2) + 4 * h;
+        const int m = mbase + (wm * TM + i) * 32 + (r16 & 3) + 8 * (r16 >> 2) + 4 * h;
         const bool ok = valid && m < a.Cout;
         const int off = ok ? (obase + (PH ? m - ph * 64 : m) * (int)a.oc) * 4 : a.out_bytes;
 #if EXTDM_X3_EXP & 4
@@ -1402,6 +1436,93 @@ bool conv_x3_forward_op(hipStream_t s, const View& out, const X3Op& in, const Pa
     else launch_sp<3, 1, 128, 128, 1, 2, 8, 2, true, 1, true>(s, a, ntiles);
   }
   return true;
+}
+
+namespace {
+
+// One two-tap launch (kernel note TT): the staged 3x3 tiles of x3_tile(3, Cout) with BX staging
+template <int TT, int BM, int BN, int WN, int NW, int NS>
+void launch_tt(hipStream_t s, const X3Args& a, unsigned ntiles, unsigned mtiles) {
+  constexpr int AH = 2 * (BM / 32) * 2 * 512;  // halves per ky' slice: two kx' steps
+  const size_t xlo = (size_t)a.XPOS * 16;
+  const size_t lds = ((size_t)2 * AH + 2 * 2 * xlo + 32 + 4 * BM) * sizeof(_Float16);
+  const auto kern = &conv_x3_kernel<3, 1, BM, BN, 1, WN, NW, 2, true, NS, false, false, 0, false, false, true, TT>;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  note_kernel("conv_x3_kernel<3, 1, %d, %d, 1, %d, %d, 2, true, %d, false, false, 0, false, false, true, %d>", BM, BN, WN,
+              NW, NS, TT);
+  hipLaunchKernelGGL(kern, dim3(ntiles, mtiles), dim3(NW * 64), lds, s, a);
+}
+
+template <int TT>
+bool launch_tt_tile(hipStream_t s, const X3Args& a, unsigned ntiles, unsigned mtiles, int bm) {
+  const int need = (a.XPOS + 255) / 256;  // staging slots per thread (4 waves)
+  if (bm == 64) {  // 64 x 256: XPOS in (256, 576]
+    if (need == 2) launch_tt<TT, 64, 256, 4, 4, 2>(s, a, ntiles, mtiles);
+    else if (need == 3) launch_tt<TT, 64, 256, 4, 4, 3>(s, a, ntiles, mtiles);
+    else return false;
+  } else {  // 128 x 128: XPOS in (128, 288]
+    if (need == 1) launch_tt<TT, 128, 128, 2, 4, 1>(s, a, ntiles, mtiles);
+    else if (need == 2) launch_tt<TT, 128, 128, 2, 4, 2>(s, a, ntiles, mtiles);
+    else return false;
+  }
+  return true;
+}
+
+// EXTDM_NO_X3_UPDOWN, read per launch decision: 1 = both kinds off, up / down = that kind off
+bool updown_off(bool up) {
+  const char* v = getenv("EXTDM_NO_X3_UPDOWN");
+  if (!v || !v[0] || v[0] == '0') return false;
+  if (v[0] == 'u' || v[0] == 'd') return (v[0] == 'u') == up;
+  return true;
+}
+
+}  // namespace
+
+bool conv_x3_updown_forward(hipStream_t s, const View& out, const View& in0, const View* in1, const PackedW& w,
+                            int stride, int pad, const ConvEpi& epi) {
+  const bool up = w.mode == MODE_DECONV;
+  if (!w.tx || in1 || (w.tbm != 64 && w.tbm != 128)) return false;
+  if (up ? (w.KH != 2 || w.KW != 2 || out.H != 2 * in0.H || out.W != 2 * in0.W)
+         : (w.mode != MODE_CONV || w.KH != 4 || w.KW != 4 || stride != 2 || pad != 1 || in0.H != 2 * out.H ||
+            in0.W != 2 * out.W))
+    return false;
+  if (in0.C % 16 != 0 || in0.C != 16 * (up ? w.tncb : w.tncb / 4) || out.C != w.M || out.B != in0.B || out.T != in0.T)
+    return false;
+  if (updown_off(up)) return false;
+  // the kernel's tile geometry: the planes it tiles (the input's for the transpose, the output's
+  // = one input phase plane for the downsample) stand in for both views of a 3x3 'same' conv
+  const int H = up ? in0.H : out.H, W = up ? in0.W : out.W;
+  View og = out, ig = in0;
+  og.H = ig.H = H;
+  og.W = ig.W = W;
+  PackedW wt;
+  wt.mode = MODE_CONV; wt.KH = wt.KW = 3;
+  wt.wx = w.tx; wt.xscale = w.tscale;
+  wt.xbm = w.tbm; wt.xbn = w.tbn; wt.xng = 1; wt.xncgb = w.tncb;
+  X3Args a;
+  unsigned ntiles = 0;
+  ConvEpi e = epi;
+  e.stats = nullptr;  // left to the caller, as on the implicit GEMM
+  if (e.res_aff || !x3_setup(og, ig, nullptr, wt, e, a, ntiles, nullptr)) return false;
+  // byte extents of the real views (x3_setup saw the stand-ins)
+  auto extent = [](const View& v, long sb, long sc, long st) {
+    return ((long)(v.B - 1) * sb + (long)(v.C - 1) * sc + (long)(v.T - 1) * st + (long)v.H * v.W) * 4;
+  };
+  const long ob = extent(out, out.sb, out.sc, out.st), ib = extent(in0, in0.sb, in0.sc, in0.st);
+  const long rb = e.res ? extent(out, e.res_sb, e.res_sc, e.res_st) : 0;
+  if (ob >= (1L << 31) - 4 || rb >= (1L << 31) - 4 || ib >= (1L << 30)) return false;
+  a.out_bytes = (int)ob;
+  a.res_bytes = (int)rb;
+  a.in0_bytes = a.in1_bytes = (int)ib;
+  if (!x3_bufx_ok(a, 16)) return false;
+  const int mtc = (out.C + w.tbm - 1) / w.tbm;
+  a.mtc = mtc;
+  a.mfast = up && ntiles % 8 == 0;  // the phases of a pixel tile back to back on one XCD (kernel note MFAST)
+  return up ? launch_tt_tile<1>(s, a, ntiles, 4u * mtc, w.tbm) : launch_tt_tile<2>(s, a, ntiles, (unsigned)mtc, w.tbm);
 }
 
 int* x3_range_ptr() {

@@ -146,6 +146,12 @@ struct PackedW {
   void* wx = nullptr;
   float* xscale = nullptr;
   int xbm = 0, xbn = 0, xng = 0, xncgb = 0;
+  // two-tap f16x3 layout [mtile][cblk][ky'][kx'][m32][hi|lo][lane][8] of the stride-2 (1,4,4) convs
+  // (pack_x3_deconv for MODE_DECONV, pack_x3_down for the 4x4 MODE_CONV; conv_x3.hip TT mode),
+  // rows undone by tscale[co]; tncb = channel blocks per m-tile
+  void* tx = nullptr;
+  float* tscale = nullptr;
+  int tbm = 0, tbn = 0, tncb = 0;
   // f16x3 implicit-GEMM layout [parity][mtile][ktile][step][m32][hi|lo][lane][8]
   // (conv_gemm_x3.hip), rows pre-scaled by powers of two undone by gscale[m]
   void* gx = nullptr;
@@ -245,6 +251,15 @@ inline size_t fea_edge_floats(int P, int C, int L) { return (size_t)P * 4 * L * 
 bool fea_edges_supported(int C, int Co, int L);
 bool fea_edges_forward(hipStream_t s, const View& out, const float* edge, int C, const void* side_w,
                        const float* side_scale, const float* corner_w, bool dry = false);
+// The stride-2 convs on the direct kernel's two-tap mode (conv_x3.hip TT): ConvTranspose(1,4,4)/s2/p1
+// (w.mode == MODE_DECONV, out 2H x 2W) as four output phases of 2x2-tap convs over the input's halo
+// tile, Conv(1,4,4)/s2/p1 (stride 2, out H/2 x W/2) as 2x2-tap convs over the four input phase
+// planes. false = not covered (no two-tap packing, a second source, Cin % 16 != 0, a W that does
+// not divide the tile, extents past 2^30 / 2^31 bytes) or sent back by EXTDM_NO_X3_UPDOWN (1 =
+// both kinds, up / down = that kind; consulted per launch): the caller falls through to
+// conv_gemm_x3_forward. The tile depends on Cout and the per-sample geometry only.
+bool conv_x3_updown_forward(hipStream_t s, const View& out, const View& in0, const View* in1, const PackedW& w,
+                            int stride, int pad, const ConvEpi& epi);
 void x3_range_reset(hipStream_t s);
 // 1x1 256 -> 256 f16x3 conv with register-resident weights (pw_x3.hip) on conv_x3's packed 1x1
 // weights (xbm 256): single input view, HW % 64 == 0, epilogue bias + ReLU only (no residual,

@@ -141,6 +141,60 @@ Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng) {
   return r;
 }
 
+// [mtile][cblk][ky'][kx'][m32][hi|lo][lane][8] of elem(mtile, row in tile, cblk, ky', kx', channel
+// in block, v): false where the layout has no element (stays zero); v comes scaled
+template <class F>
+static std::vector<half_t> pack_two_tap(int mt, int cblks, int bm, F&& elem) {
+  const int m32 = bm / 32;
+  std::vector<half_t> g((size_t)mt * cblks * 4 * m32 * 1024);
+  for (int mtile = 0; mtile < mt; ++mtile)
+    for (int cb = 0; cb < cblks; ++cb)
+      for (int ky = 0; ky < 2; ++ky)
+        for (int kx = 0; kx < 2; ++kx)
+          for (int q = 0; q < m32; ++q)
+            for (int l = 0; l < 64; ++l)
+              for (int e = 0; e < 8; ++e) {
+                float v;
+                if (!elem(mtile, q * 32 + (l & 31), cb, ky, kx, 8 * (l >> 5) + e, v)) continue;
+                const size_t base = (((((size_t)mtile * cblks + cb) * 2 + ky) * 2 + kx) * m32 + q) * 2;
+                put_hilo(&g[base * 512 + l * 8 + e], v);
+              }
+  return g;
+}
+
+Frags pack_x3_deconv(const fvec& w, int ci, int co, int bm) {
+  const int ncb = (ci + 15) / 16, mtc = (co + bm - 1) / bm;
+  Frags r{{}, fvec(co), ncb};
+  fvec scale(co);
+  for (int m = 0; m < co; ++m) {
+    float mx = 0.f;
+    for (int c = 0; c < ci; ++c)
+      for (int tap = 0; tap < 16; ++tap) mx = std::max(mx, std::fabs(w[((size_t)c * co + m) * 16 + tap]));
+    scale[m] = std::ldexp(1.f, pow2_row_exp(mx, r.rs[m]));
+  }
+  r.g = pack_two_tap(4 * mtc, ncb, bm, [&](int mtile, int row, int cb, int ky, int kx, int cc, float& v) {
+    const int ph = mtile / mtc, m = (mtile % mtc) * bm + row, c = cb * 16 + cc;
+    if (m >= co || c >= ci) return false;
+    v = w[(((size_t)c * co + m) * 4 + 3 - (ph >> 1) - 2 * ky) * 4 + 3 - (ph & 1) - 2 * kx] * scale[m];
+    return true;
+  });
+  return r;
+}
+
+Frags pack_x3_down(const fvec& w, int co, int ci, int bm) {
+  const int ncb = (ci + 15) / 16, mt = (co + bm - 1) / bm;
+  Frags r{{}, fvec(co), 4 * ncb};
+  fvec scale(co);
+  for (int m = 0; m < co; ++m) scale[m] = std::ldexp(1.f, row_exp(&w[(size_t)m * ci * 16], (size_t)ci * 16, r.rs[m]));
+  r.g = pack_two_tap(mt, 4 * ncb, bm, [&](int mtile, int row, int cblk, int ky, int kx, int cc, float& v) {
+    const int q = cblk / ncb, m = mtile * bm + row, c = (cblk % ncb) * 16 + cc;
+    if (m >= co || c >= ci) return false;
+    v = w[(((size_t)m * ci + c) * 4 + 2 * ky + 1 - (q >> 1)) * 4 + 2 * kx + 1 - (q & 1)] * scale[m];
+    return true;
+  });
+  return r;
+}
+
 HaloPack pack_halo(const fvec& w, int ks, int co, int ci, int bm, int ch) {
   const int kk = ks * ks, cib = 2 * ch, stages = (ci + cib - 1) / cib, mt = (co + bm - 1) / bm;
   const size_t afl = (size_t)ch * kk * 2 * bm;

@@ -1,7 +1,7 @@
 // Weight layouts of the MFMA / VALU kernels as pure host functions (no HIP, no kernels.h): host
 // vectors and the tile parameters the kernel files choose in, host vectors out. runtime.cpp,
-// fvd.cpp and lpips.cpp upload the results; tests/pack_driver.cpp and tests/pack_lpips_driver.cpp
-// run the same functions on the CPU.
+// fvd.cpp and lpips.cpp upload the results; tests/pack_driver.cpp, tests/pack_lpips_driver.cpp and
+// tests/pack_updown_driver.cpp run the same functions on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -82,6 +82,18 @@ Frags pack_conv2d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int s
 // f16x3 layout (conv_x3.hip): [mtile][cb*KS + ky][(g, kx)][m32][hi|lo][lane][8], lane = (h, lc): row
 // m = mtile*BM + m32*32 + lc, input channel cb*16NG + g*16 + 8h + e. Rows scaled as in pack_frags.
 Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng);
+// Two-tap f16x3 layouts (conv_x3.hip, TT mode): the stride-2 (1,4,4)/p1 convs as sums of 2x2-tap
+// stride-1 convs over a 3x3-style halo tile, [mtile][cblk][ky'][kx'][m32][hi|lo][lane][8] with 16
+// input channels per block (lane = (h, lc): channel 16*cb + 8h + e) and rows scaled by 2^s(co)
+// over the whole 4x4 kernel, undone by rs[co]; Frags::n = channel blocks per m-tile.
+// ConvTranspose W[ci][co][1][4][4]: mtile = ph*MTC + ct (ph = 2py + px the output phase, MTC =
+// ceil(co / bm)), row co = ct*bm + m32*32 + lc, cblk = cb < ci/16; element
+// W[16cb + 8h + e][co][3 - py - 2ky'][3 - px - 2kx'] (the taps of pack_deconv_planes).
+Frags pack_x3_deconv(const fvec& w, int ci, int co, int bm);
+// Downsample W[co][ci][1][4][4]: mtile = ct, row co = ct*bm + m32*32 + lc, cblk = q*(ci/16) + cb
+// (q = 2qy + qx the input phase plane in[2Y + qy][2X + qx]); element
+// W[co][16cb + 8h + e][2ky' + 1 - qy][2kx' + 1 - qx].
+Frags pack_x3_down(const fvec& w, int co, int ci, int bm);
 // Direct-conv layout [mtile][stage][step][half][BM]: step = (cp*k + ky)*k + kx,
 // input channel = stage*2CH + half*CH + cp (conv_halo.hip).
 struct HaloPack { fvec a; int stages = 0; };

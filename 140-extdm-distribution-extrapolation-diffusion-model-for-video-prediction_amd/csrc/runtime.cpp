@@ -182,6 +182,10 @@ struct ExtdmHandle {
       pw.xbm = tl.bm; pw.xbn = tl.bn; pw.xng = tl.ng; pw.xncgb = x.n;
     }
     if (x3_convs()) upload_gemm_x3(pw, a, 1);
+    if (x3_convs() && kh == 4 && kw == 4 && ci % 16 == 0) {  // Downsample: the direct kernel's two-tap mode
+      const X3Tile tl = x3_tile(3, co);
+      upload_two_tap(pw, pack_x3_down(t.f, co, ci, tl.bm), tl);
+    }
     if (kh == kw && narrow_cot(kh, co) > 0) {
       pw.vcot = narrow_cot(kh, co);
       pw.wv = upload(pack_narrow(t.f, kh * kw, co, ci, pw.vcot));
@@ -225,7 +229,17 @@ struct ExtdmHandle {
     PackedW pw = gemm_weight(a, co, ci * 4);
     pw.KH = 2; pw.KW = 2; pw.mode = MODE_DECONV;
     if (x3_convs()) upload_gemm_x3(pw, a, 4);
+    if (x3_convs() && ci % 16 == 0) {
+      const X3Tile tl = x3_tile(3, co);
+      upload_two_tap(pw, pack_x3_deconv(t.f, ci, co, tl.bm), tl);
+    }
     return packed[n] = pw;
+  }
+  // the two-tap slices of a stride-2 conv (conv_x3.hip TT) on the 3x3 tile tl
+  void upload_two_tap(PackedW& pw, const Frags& x, const X3Tile& tl) {
+    pw.tx = upload(x.g);
+    pw.tscale = upload(x.rs);
+    pw.tbm = tl.bm; pw.tbn = tl.bm == 64 ? 256 : 128; pw.tncb = x.n;
   }
 
   // init_conv's x-branch composed with init_noise_conv (xpath_x3.hip, pack_xpath)
@@ -2404,6 +2418,40 @@ int extdm_bench_layer(ExtdmHandle* h, int B, int layer, int iters, float* ms_out
       (void)hipEventDestroy(e1);
       *ms_out = ms / iters;
       *flops_out = flop;
+      return;
+    }
+    // layers 18 / 19: the level-0 stride-2 convs as the forward issues them: 18 = the last
+    // Upsample (ConvTranspose (1,4,4)/s2/p1, L/2 -> L), 19 = the first Downsample (L -> L/2)
+    if (layer == 18 || layer == 19) {
+      const bool upl = layer == 18;
+      const std::string ix = h->cfg.arch == EXTDM_ARCH_ADA_U22 ? ".6" : ".5";
+      const std::string pre = upl ? "ups." + std::to_string(h->cfg.n_levels - 2) + ix : "downs.0" + ix;
+      REQUIRE(h->cfg.n_levels >= 2 && h->has(pre + ".weight"), "bench layer weight missing: " + pre + ".weight");
+      const auto& sh = h->H(pre + ".weight").shape;
+      const int c_in = (int)sh[upl ? 0 : 1], c_out = (int)sh[upl ? 1 : 0];
+      const int Li = upl ? L / 2 : L, Lo = upl ? L : L / 2;
+      View in = h->alloc_cf(B, c_in, T, Li, Li), out = h->alloc_cf(B, c_out, T, Lo, Lo);
+      fill_normal(s, in.p, 1, (int)in.numel(), 17, 0, 0, 1);
+      const PackedW& w = upl ? h->Pdeconv(pre + ".weight") : h->P(pre + ".weight");
+      float* bias = h->D(pre + ".bias");
+      auto launch = [&, in, out] { h->conv(out, in, nullptr, w, upl ? 1 : 2, upl ? 0 : 1, bias); };
+      note_kernel("");
+      launch();  // warm
+      h->bench_kernel[layer] = noted_kernel();
+      hipEvent_t e0, e1;
+      HIPCHK(hipEventCreate(&e0));
+      HIPCHK(hipEventCreate(&e1));
+      HIPCHK(hipEventRecord(e0, s));
+      for (int i = 0; i < iters; ++i) launch();
+      HIPCHK(hipEventRecord(e1, s));
+      HIPCHK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      *ms_out = ms / iters;
+      // 16 taps per output pixel (Downsample) = 4 taps per output pixel of each phase (Upsample)
+      *flops_out = 2.0 * B * T * (double)(upl ? Li : Lo) * (upl ? Li : Lo) * (double)c_out * c_in * 16;
       return;
     }
     static const char* names[] = {"init_conv.weight", "downs.0.0.block2.proj.weight", "downs.1.0.block2.proj.weight",
