@@ -82,6 +82,7 @@ struct X3Args {
   int mtc;  // TT = 1: m-tiles per output phase
   int in0_bytes, in1_bytes;  // BUFX: byte extents of the two sources (< 2^30), 0 = not usable
   ConvEpi e;
+  int aff_ns;  // AFF = 1: table rows (samples) a tile's planes span at most
 };
 
 __device__ __forceinline__ float act_apply(float v, int act) {
@@ -183,8 +184,19 @@ template <> struct XMaxX3<5, 256> { static constexpr int v = 400; };
 // (q, cb) stages the phase plane in[2 iy + qy][2 ix + qx] (the phase's qy Win + qx in the buffer
 // loads' scalar offset; a position is inside the image independently of the phase) and reads it
 // from origin (1 - qy, 1 - qx). BX staging only.
+// AFF: input affine v = (x - m) * r applied to the staged values in store_x, before the hi / lo
+// split and the range check, from the float2 (m, r) table ConvEpi::in_aff (BX staging only). A
+// position outside the image takes the pair (0, 0): the buffer load gave 0 and the padding stays
+// exactly 0 in the normalised domain. 1 = per (sample, channel), table [B][Cin] (the MotionAdaptor
+// extrapolators: m = mean, r = 1 / std; the normalised tensor is never written): the rows of the
+// samples the tile's planes span are copied into LDS in the prologue, a slot reads its 16 pairs of
+// the channel block from there (a slot outside the image from a 16-pair zero row); the epilogue is
+// out = post_scale * (acc * scale + bias) + res (ConvEpi::post_first; post_shift unused; with
+// split-K the SPL = 1 slices stage with the affine and the SPL = 2 sum takes this epilogue). 2 = per
+// pixel, table [P][H W] (channel LayerNorm ahead of a 1x1 conv, gamma folded into the weight: m =
+// mean, r = 1 / sqrt(var + eps)): one pair per staging slot, loaded once in the prologue.
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF, bool SPAN, int NS, bool XOP = false,
-          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false, int TT = 0>
+          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false, int TT = 0, int AFF = 0>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 && KS == 5 ? 2 : 1))) void conv_x3_kernel(X3Args a) {
   constexpr int NT = NW * 64;
   constexpr int PAD = KS / 2;
@@ -203,6 +215,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   constexpr int TN = BN / (32 * WN);
   static_assert(TM >= 1 && TN >= 1 && WM * WN == NW, "bad tile");
   static_assert(!XOP || (NG == 1 && XBUF == 2 && SPAN), "operand input: one group, two X buffers");
+  static_assert(!AFF || (SPAN && BX && !XOP && !WS && !PH && TT == 0 && (AFF == 2 ? SPL != 2 : NG == 1)),
+                "AFF: buffer-load staging (SPL = 2 with AFF = 1: the epilogue order alone)");
 
   extern __shared__ __attribute__((aligned(16))) _Float16 smx[];
   // halves from an X slot's hi block to its lo block (DMA mode: two c8 planes of whole
@@ -272,10 +286,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
 
   // ---- staging slots: (group, halo position), 16 channels each ----
   int sg[NSLOT], spos[NSLOT], soff0[NSLOT], soff1[NSLOT];
+  // AFF = 1: the slot's table row in LDS (floats from atab; < 0: outside the image); AFF = 2: its pair
+  int arow[NSLOT];
+  float2 amr[NSLOT];
 #pragma unroll
   for (int j = 0; j < NSLOT; ++j) {
     const int sl = tid + NT * j;
     sg[j] = -1; spos[j] = 0; soff0[j] = -1; soff1[j] = -1;
+    arow[j] = -1; amr[j] = make_float2(0.f, 0.f);
     if (sl < a.XPOS * NG) {
       const int g = sl / a.XPOS, pos = sl - g * a.XPOS;
       const int p = pos / (THK * a.RS);
@@ -289,6 +307,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
         const int ip = TT == 2 ? 4 * iy * a.W + 2 * ix : iy * a.W + ix;  // TT = 2: phase (0, 0) of the 2H x 2W input
         soff0[j] = (int)((long)b * a.i0b + (long)t * a.i0t) + ip;
         soff1[j] = (int)((long)b * a.i1b + (long)t * a.i1t) + ip;
+        if (AFF == 1) arow[j] = (b - plane0 / a.T) * a.Cin * 2;
+        if (AFF == 2) amr[j] = a.e.in_aff[(long)q * (a.H * a.W) + ip];
       }
     }
   }
@@ -400,6 +420,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   // pending on one path, and hipcc's path-insensitive wait analysis then drains vmcnt(0)
   // at the next channel block's X prefetch.
   _Float16* const xdummy = Xs0 + XB * XH + (WSR ? 2 * 16 * RP : 0);  // 32 halves, then the epilogue's scale/bias rows
+  // AFF = 1: the (m, r) rows of the tile's samples [aff_ns][Cin], then 16 zero pairs (behind the
+  // epilogue's scale / bias rows)
+  float* const atab = reinterpret_cast<float*>(xdummy + 32) + 2 * BM;
+  float* const azero = atab + a.aff_ns * a.Cin * 2;
   auto store_x = [&](_Float16* Xs, int cgb) __attribute__((always_inline)) {
 #pragma unroll
     for (int j = 0; j < NSLOT; ++j) {
@@ -415,6 +439,19 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
           if (!bufx) r *= xmask(j, cgb, c);  // bufx: outside positions already loaded as 0
         }
         v[c] = r;
+      }
+      if (AFF == 1) {
+        const float* tp = arow[j] >= 0 ? atab + arow[j] + cgb * (2 * CIB) : azero;
+#pragma unroll
+        for (int c = 0; c < 16; c += 2) {
+          const float4 mr = *reinterpret_cast<const float4*>(tp + 2 * c);
+          v[c] = (v[c] - mr.x) * mr.y;
+          v[c + 1] = (v[c + 1] - mr.z) * mr.w;
+        }
+      }
+      if (AFF == 2) {
+#pragma unroll
+        for (int c = 0; c < 16; ++c) v[c] = (v[c] - amr[j].x) * amr[j].y;
       }
       unsigned hw[8], lw[8];
       float am = 0.f;
@@ -562,6 +599,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     const int mc = m < a.Cout ? m : a.Cout - 1;
     ep_sc[tid] = a.wscale[mc];
     ep_bi[tid] = a.e.bias ? a.e.bias[mc] : 0.f;
+  }
+  if (AFF == 1 && SPL != 2) {
+    // rows bf .. bf + aff_ns - 1 of the table are contiguous; a sample past the batch reads zeros
+    const int bf = plane0 / a.T, nb = a.P / a.T;
+    float2* const at2 = reinterpret_cast<float2*>(atab);
+    for (int i = tid; i < a.aff_ns * a.Cin; i += NT)
+      at2[i] = bf + i / a.Cin < nb ? a.e.in_aff[(long)bf * a.Cin + i] : make_float2(0.f, 0.f);
+    if (tid < 16) at2[a.aff_ns * a.Cin + tid] = make_float2(0.f, 0.f);
+    __syncthreads();  // before the first store_x
   }
   if (SPL == 2) {
     // sum of the slices' partial accumulators, in slice order
@@ -811,6 +857,13 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       float v[16];
 #pragma unroll
       for (int r16 = 0; r16 < 16; ++r16) v[r16] = acc[i][j][r16] * scl[r16] + bia[r16];
+      if (AFF == 1 && has_post) {  // ConvEpi::post_first: the conv term alone is scaled, then + res
+        float ps[16];
+#pragma unroll
+        for (int r16 = 0; r16 < 16; ++r16) ps[r16] = a.e.post_scale[post_pc ? mrow[r16] : b * a.Cout + mrow[r16]];
+#pragma unroll
+        for (int r16 = 0; r16 < 16; ++r16) v[r16] = v[r16] * ps[r16];
+      }
       if (has_res) {
         const int rbase = (int)((long)b * a.e.res_sb + (long)t * a.e.res_st) + pix;
         float rv[16];
@@ -829,7 +882,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
 #pragma unroll
         for (int r16 = 0; r16 < 16; ++r16) v[r16] += rv[r16];
       }
-      if (has_post) {
+      if (AFF != 1 && has_post) {
         float ps[16], pt[16];
 #pragma unroll
         for (int r16 = 0; r16 < 16; ++r16) {
@@ -1048,13 +1101,13 @@ int x3_v3() {
 // 3x3 128 x 128 tile on 4 waves of 64 x 64 (12 MFMAs per 8 ds_read_b128, two workgroups per
 // CU) when its LDS fits half a CU; else 8 waves of 32 x 64 at one workgroup per CU.
 // EXTDM_X3_W128=8 keeps the 8-wave tile everywhere (A/B).
-bool x3_w128_4(const X3Args& a, bool xop) {
+bool x3_w128_4(const X3Args& a, bool xop, size_t extra_halves = 0) {
   static const int w = [] { const char* v = getenv("EXTDM_X3_W128"); return v ? atoi(v) : 4; }();
   if (w == 8) return false;
   constexpr size_t AH = 3 * 4 * 2 * 512;
   const size_t xlo = xop ? (size_t)((a.XPOS + 63) & ~63) * 16
                          : (EXTDM_X3_LIN == 1 ? (size_t)((a.XPOS + 1 + 63) & ~63) * 16 : (size_t)a.XPOS * 16);
-  return (2 * AH + 2 * 2 * xlo + 32 + 4 * 128) * sizeof(_Float16) <= 80 * 1024;
+  return (2 * AH + 2 * 2 * xlo + 32 + 4 * 128 + extra_halves) * sizeof(_Float16) <= 80 * 1024;
 }
 // split-K thresholds of the 3x3 128-row tile (launch_wg, total_wg): 8 waves at one workgroup
 // per CU split below 128 workgroups, up to 256; the 4-wave tile (two per CU) below
@@ -1215,8 +1268,141 @@ bool x3_bn256(const View& out, const PackedW& w, const ConvEpi& epi) {
   return nwg >= 192;
 }
 
+namespace {
+
+// One launch with the input affine (kernel note AFF): KY = 1, two X buffers, spanning barriers, BX staging
+template <int KS, int BM, int BN, int NG, int WN, int NW, int NS, int SPL, int AFF>
+void launch_aff(hipStream_t s, const X3Args& a, unsigned ntiles, size_t lds) {
+  const auto kern = &conv_x3_kernel<KS, 1, BM, BN, NG, WN, NW, 2, true, NS, false, false, SPL, false, false, true, 0, AFF>;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  note_kernel("conv_x3_kernel<%d, 1, %d, %d, %d, %d, %d, 2, true, %d, false, false, %d, false, false, true, 0, %d>", KS, BM,
+              BN, NG, WN, NW, NS, SPL, AFF);
+  hipLaunchKernelGGL(kern, dim3(ntiles, (a.Cout + BM - 1) / BM, SPL == 1 ? a.nsplit : 1), dim3(NW * 64), lds, s, a);
+}
+
+// Geometry of an input-affine launch (x3_setup plus the AFF preconditions); false: not covered, the
+// caller keeps its separate normalisation pass. The decision reads the views, the weight's tile and
+// the process-wide switches only, so a planner's dry run and every forward agree. *lds: the launch's
+// dynamic LDS bytes; *split: the split-K slices of the 1x1 tiles (0: none), a function of the
+// per-sample geometry (split_slices).
+bool x3_aff_setup(const View& out, const View& in0, const View* in1, const PackedW& w, const ConvEpi& epi, int mode,
+                  X3Args& a, unsigned& ntiles, size_t* lds, int* split) {
+  // A 1x1 conv written over one of its own sources (the MotionAdaptor's fuser): a workgroup reads its
+  // pixel tile's channels before it writes them, but a second m-tile of the same pixels would read
+  // what the first one wrote -- one m-tile only
+  if (out.p == in0.p || (in1 && out.p == in1->p)) {
+    if (mode != 2 || out.C > w.xbm || out.sb != (out.p == in0.p ? in0.sb : in1->sb)) return false;
+  }
+  static const bool nospan = env_flag("EXTDM_X3_NOSPAN");
+  if (nospan || EXTDM_X3_LIN == 1 || (mode != 1 && mode != 2)) return false;
+  if (!x3_setup(out, in0, in1, w, epi, a, ntiles, nullptr) || a.e.stats) return false;
+  const int ks = w.KH, bm = w.xbm, bn = w.xbn, ng = w.xng;
+  if (!x3_bufx_ok(a, 16 * ng) || epi.res_aff) return false;
+  size_t tab = 0;  // halves of the LDS table
+  *split = 0;
+  if (mode == 1) {
+    // 3x3, one source, the 64 x 256 and the 4-wave 128 x 128 tiles (the latter with its split-K)
+    if (ks != 3 || ng != 1 || in1 || x3_v3() == 1 || x3_ws(kWsStaged64)) return false;
+    a.aff_ns = a.T % a.NP == 0 ? 1 : (a.NP % a.T == 0 ? a.NP / a.T : (a.NP + a.T - 2) / a.T + 1);
+    tab = ((size_t)a.aff_ns * a.Cin + 16) * 4;
+    if (bm == 64 && bn == 256) {
+      if ((a.XPOS + 255) / 256 > 3) return false;
+    } else if (bm == 128 && bn == 128) {
+      long mw, mt;
+      x3_split128(true, mw, mt);
+      if (!x3_w128_4(a, false, tab)) return false;
+      *split = split_slices(a, ntiles, mw, mt);
+    } else {
+      return false;
+    }
+  } else {
+    if (ks != 1 || ng != 2 || a.XPOS > bn) return false;
+    if (bm == 256 && bn == 128) *split = x3_split256() ? split_slices(a, ntiles, 256, 256, 256) : 0;
+    else if (bm == 128 && bn == 128) *split = split_slices(a, ntiles, 384, 512);
+    else if (!((bm == 64 && bn == 128) || (bm == 256 && bn == 256))) return false;
+  }
+  const size_t AH = (size_t)ng * ks * (bm / 32) * 2 * 512;
+  const size_t lds0 = (2 * AH + 2 * 2 * (size_t)a.XPOS * ng * 16 + 32 + 4 * bm) * sizeof(_Float16);
+  *lds = lds0 + tab * sizeof(_Float16);
+  // the table must not cost the tile a workgroup per CU (160 KB of LDS)
+  return *lds <= 160 * 1024 && (160 * 1024) / *lds == (160 * 1024) / lds0;
+}
+
+bool conv_x3_forward_aff(hipStream_t s, const View& out, const View& in0, const View* in1, const PackedW& w,
+                         const ConvEpi& epi) {
+  X3Args a;
+  unsigned ntiles = 0;
+  size_t lds = 0;
+  int S = 0;
+  const int mode = epi.in_aff_mode;
+  if (!epi.in_aff || !x3_aff_setup(out, in0, in1, w, epi, mode, a, ntiles, &lds, &S)) return false;
+  if (mode == 1) {
+    if (!epi.post_first || !epi.post_scale || !epi.res) return false;
+    const int need = (a.XPOS + 255) / 256;
+    if (w.xbm == 64) {
+      if (need <= 1) launch_aff<3, 64, 256, 1, 4, 4, 1, 0, 1>(s, a, ntiles, lds);
+      else if (need == 2) launch_aff<3, 64, 256, 1, 4, 4, 2, 0, 1>(s, a, ntiles, lds);
+      else launch_aff<3, 64, 256, 1, 4, 4, 3, 0, 1>(s, a, ntiles, lds);
+    } else if (S) {  // the slices normalise while they stage, their sum takes the post_first epilogue
+      if (!epi.split_ws || split_bytes(a, ntiles, S) > epi.split_ws_bytes) return false;
+      a.part = epi.split_ws;
+      a.nsplit = S;
+      if (need <= 1) launch_aff<3, 128, 128, 1, 2, 4, 1, 1, 1>(s, a, ntiles, lds);
+      else launch_aff<3, 128, 128, 1, 2, 4, 2, 1, 1>(s, a, ntiles, lds);
+      launch_aff<3, 128, 128, 1, 2, 4, 1, 2, 1>(s, a, ntiles, lds);
+    } else {
+      if (need <= 1) launch_aff<3, 128, 128, 1, 2, 4, 1, 0, 1>(s, a, ntiles, lds);
+      else launch_aff<3, 128, 128, 1, 2, 4, 2, 0, 1>(s, a, ntiles, lds);
+    }
+    return true;
+  }
+  if (epi.post_first) return false;
+  a.mfast = x3_mfast(a, X3Tile{w.xbm, w.xbn, w.xng}, ntiles);
+  if (S) {  // the slices with the affine, their sum as on the plain route
+    if (!epi.split_ws || split_bytes(a, ntiles, S) > epi.split_ws_bytes) return false;
+    a.part = epi.split_ws;
+    a.nsplit = S;
+    if (w.xbm == 256) {
+      launch_aff<1, 256, 128, 2, 2, 8, 1, 1, 2>(s, a, ntiles, lds);
+      launch_sp<1, 1, 256, 128, 2, 2, 8, 2, true, 1, false, false, 2>(s, a, ntiles);
+    } else {
+      launch_aff<1, 128, 128, 2, 2, 4, 1, 1, 2>(s, a, ntiles, lds);
+      launch_sp<1, 1, 128, 128, 2, 2, 4, 2, true, 1, false, false, 2>(s, a, ntiles);
+    }
+    return true;
+  }
+  if (w.xbm == 64) launch_aff<1, 64, 128, 2, 4, 4, 1, 0, 2>(s, a, ntiles, lds);
+  else if (w.xbm == 128) launch_aff<1, 128, 128, 2, 2, 4, 1, 0, 2>(s, a, ntiles, lds);
+  else if (w.xbn == 256) launch_aff<1, 256, 256, 2, 2, 8, 1, 0, 2>(s, a, ntiles, lds);
+  else launch_aff<1, 256, 128, 2, 2, 8, 1, 0, 2>(s, a, ntiles, lds);
+  return true;
+}
+
+}  // namespace
+
+bool conv_x3_aff_covers(const View& out, const View& in0, const View* in1, const PackedW& w0, int mode) {
+  if (!w0.wx || w0.mode != MODE_CONV || w0.KH != w0.KW) return false;
+  PackedW wt = w0;
+  if (x3_bn256(out, w0, ConvEpi{})) wt.xbn = 256;
+  X3Args a;
+  unsigned ntiles = 0;
+  size_t lds = 0;
+  int S = 0;
+  return x3_aff_setup(out, in0, in1, wt, ConvEpi{}, mode, a, ntiles, &lds, &S);
+}
+
 bool conv_x3_forward(hipStream_t s, const View& out, const View& in0, const View* in1, const PackedW& w0,
                      const ConvEpi& epi, int* stats_slots) {
+  if (epi.in_aff_mode) {
+    if (stats_slots) *stats_slots = 0;
+    PackedW wa = w0;
+    if (x3_bn256(out, w0, epi)) wa.xbn = 256;
+    return conv_x3_forward_aff(s, out, in0, in1, wa, epi);
+  }
   PackedW wt = w0;
   if (x3_bn256(out, w0, epi)) wt.xbn = 256;
   const PackedW& w = wt;

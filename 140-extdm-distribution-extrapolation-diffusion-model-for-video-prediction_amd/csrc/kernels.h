@@ -190,6 +190,13 @@ struct ConvEpi {
   // conv of the stream in turn
   float* split_ws = nullptr;
   size_t split_ws_bytes = 0;
+  // Input affine of conv_x3's staged path (kernel note AFF; conv_x3_forward only, where
+  // conv_x3_aff_covers holds): the conv reads v = (x - m) * r with (m, r) = in_aff[...], 1 = per
+  // (sample, channel) [B][Cin], 2 = per pixel [B][T][H W]. post_first (mode 1 only, and required
+  // there): out = post_scale * (acc * scale + bias) + res, post_shift unused.
+  int in_aff_mode = 0;
+  const float2* in_aff = nullptr;
+  int post_first = 0;
 };
 
 // Input channels per half-stage of the halo conv for kernel size ks and tile bm.
@@ -209,6 +216,9 @@ bool conv_x3_forward(hipStream_t s, const View& out, const View& in0, const View
                      const ConvEpi& epi, int* stats_slots = nullptr);
 // Whether conv_x3_forward covers this stride-1 'same' conv (no launch).
 bool conv_x3_covers(const View& out, const View& in0, const View* in1, const PackedW& w);
+// Whether conv_x3_forward covers this conv with the input affine `mode` (ConvEpi::in_aff_mode; no
+// launch): the 64 x 256 and 4-wave 128 x 128 3x3 tiles for mode 1, the 1x1 tiles for mode 2, buffer-load staging.
+bool conv_x3_aff_covers(const View& out, const View& in0, const View* in1, const PackedW& w, int mode);
 // Split-K partial bytes the conv will use (0: no split) -- ConvEpi::split_ws must hold them.
 size_t conv_x3_split_bytes(const View& out, const View& in0, const View* in1, const PackedW& w);
 size_t conv_x3_op_split_bytes(const View& out, const PackedW& w, int C);
@@ -442,6 +452,13 @@ void bilinear_frames(hipStream_t s, const View& dst, const View& a, const View& 
 // per (b,c) mean and unbiased std (+eps) over T*H*W (u12:670-678)
 void adaptor_stats(hipStream_t s, const View& x, float* mean, float* std_, double* partials);
 void adaptor_normalize(hipStream_t s, const View& dst, const View& src, const float* mean, const float* std_);
+// The same statistics carried across extrapolators: x = the frames written since the last call, n_prev
+// = elements per (b, c) already in carry [B C] (0: none). Writes carry = (mean, M2) in double, mr =
+// (mean, 1 / std) [B][C] (conv_x3's input affine, mode 1) and std [B][C].
+void adaptor_stats_inc(hipStream_t s, const View& x, long n_prev, double2* carry, float2* mr, float* std_);
+// Per-pixel (mean, 1 / sqrt(var + 1e-5)) of channel_ln's normalisation over in0 ++ in1, [B][T][H W]
+// (conv_x3's input affine, mode 2), in channel_ln's summation order.
+void channel_ln_stats(hipStream_t s, float2* out, const View& in0, const View* in1);
 // zero frames 0 and T - 1 of every clip of a frame-major buffer (one launch; a 2-D memset of the
 // same rows ran at ~0.2 TB/s)
 void zero_pad_frames(hipStream_t s, const View& x);

@@ -433,6 +433,86 @@ __global__ __launch_bounds__(256) void channel_ln4_kernel(float* out, long osb, 
   }
 }
 
+// The statistics of the same LayerNorm alone, for a 1x1 conv that normalises while it stages
+// (conv_x3.hip AFF = 2, gamma folded into its weight): one read of the sources, one float2
+// (mean, 1 / sqrt(var + eps)) per pixel. Blocks, loads and the per-pixel summation order are
+// channel_ln4_kernel's, so the mean and the denominator are the ones it would normalise with.
+__global__ __launch_bounds__(256) void channel_ln_stats4_kernel(float2* out, const float* p0, long sb0, long sc0,
+                                                                long st0, int C0, const float* p1, long sb1,
+                                                                long sc1, long st1, int C, int T, int HW, int B) {
+  __shared__ double red[8][32][4], red2[8][32][4];
+  const int q = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  const long nq = (long)B * T * HW / 4;
+  const long idx = (long)blockIdx.x * 32 + q;
+  const bool ok = idx < nq;
+  const long pix = (ok ? idx : 0) * 4;
+  const int hw = (int)(pix % HW);
+  const int t = (int)((pix / HW) % T);
+  const int b = (int)(pix / ((long)HW * T));
+  const long b0 = (long)b * sb0 + (long)t * st0 + hw;
+  const long b1 = (long)b * sb1 + (long)t * st1 + hw;
+  double s[4] = {0.0, 0.0, 0.0, 0.0}, ss[4] = {0.0, 0.0, 0.0, 0.0};
+  if (ok) {
+#pragma unroll 4
+    for (int c = grp; c < C; c += 8) {
+      const float4 v = c < C0 ? *reinterpret_cast<const float4*>(p0 + b0 + (long)c * sc0)
+                              : *reinterpret_cast<const float4*>(p1 + b1 + (long)(c - C0) * sc1);
+      const double d[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) { s[k] += d[k]; ss[k] += d[k] * d[k]; }
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) { red[grp][q][k] = s[k]; red2[grp][q][k] = ss[k]; }
+  __syncthreads();
+  if (threadIdx.x < 128) {
+    const int qq = threadIdx.x >> 2, k = threadIdx.x & 3;
+    const long px = ((long)blockIdx.x * 32 + qq) * 4 + k;
+    double tt = 0.0, t2 = 0.0;
+    for (int i = 0; i < 8; ++i) { tt += red[i][qq][k]; t2 += red2[i][qq][k]; }
+    const double mean = tt / C;
+    double var = t2 / C - mean * mean;
+    if (var < 0) var = 0;
+    if (px < nq * 4) out[px] = make_float2((float)mean, 1.f / sqrtf((float)var + 1e-5f));
+  }
+}
+
+// the scalar form (channel_ln_kernel's blocks and summation order)
+__global__ __launch_bounds__(256) void channel_ln_stats_kernel(float2* out, const float* p0, long sb0, long sc0,
+                                                               long st0, int C0, const float* p1, long sb1,
+                                                               long sc1, long st1, int C, int T, int HW, int B) {
+  __shared__ double red[8][33], red2[8][33];
+  const int px = threadIdx.x & 31, grp = threadIdx.x >> 5;
+  const long idx = (long)blockIdx.x * 32 + px;
+  const long npix = (long)B * T * HW;
+  const bool ok = idx < npix;
+  const long id2 = ok ? idx : 0;
+  const int hw = (int)(id2 % HW);
+  const int t = (int)((id2 / HW) % T);
+  const int b = (int)(id2 / ((long)HW * T));
+  const long b0 = (long)b * sb0 + (long)t * st0 + hw;
+  const long b1 = (long)b * sb1 + (long)t * st1 + hw;
+  double s = 0.0, ss = 0.0;
+  if (ok)
+    for (int c = grp; c < C; c += 8) {
+      const double v = ld2(p0, b0, sc0, C0, p1, b1, sc1, c);
+      s += v;
+      ss += v * v;
+    }
+  red[grp][px] = s;
+  red2[grp][px] = ss;
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    const long o = (long)blockIdx.x * 32 + threadIdx.x;
+    double tt = 0.0, t2 = 0.0;
+    for (int i = 0; i < 8; ++i) { tt += red[i][threadIdx.x]; t2 += red2[i][threadIdx.x]; }
+    const double mean = tt / C;
+    double var = t2 / C - mean * mean;
+    if (var < 0) var = 0;
+    if (o < npix) out[o] = make_float2((float)mean, 1.f / sqrtf((float)var + 1e-5f));
+  }
+}
+
 // 32 pixels per block, 8 channel groups per pixel (thread = (pixel, group)), so a
 // LayerNorm over hundreds of channels at few pixels still fills the machine.
 __global__ __launch_bounds__(256) void channel_ln_kernel(float* out, long osb, long osc, long ost,
@@ -778,6 +858,52 @@ __global__ __launch_bounds__(256) void adaptor_stats_kernel(const float* x, long
   }
 }
 
+// The same statistics carried from one extrapolator to the next: x holds the T frames written since
+// the last call (the whole prefix on the first one). One pass gives the chunk's (count, mean, M2)
+// in double -- sums of x - k and (x - k)^2 with k the chunk's first element, so the one-pass M2
+// does not cancel when |mean| >> std -- which Chan's formula combines with the carried (mean, M2)
+// of the n_prev earlier elements, always as (earlier, chunk). No atomics; the element-to-thread
+// map and the reduction tree depend on (T, HW) alone. Writes carry = (mean, M2) of the n_prev + T HW
+// elements, mr = (mean, 1 / std) for the conv's input affine and std for its epilogue, with
+// std = sqrt(M2 / (n - 1) + 1e-5) as adaptor_stats_kernel.
+__global__ __launch_bounds__(256) void adaptor_stats_inc_kernel(const float* x, long sb, long sc, long st, int C, int T,
+                                                                int HW, long n_prev, double2* carry, float2* mr,
+                                                                float* std_out) {
+  const int bc = blockIdx.x;
+  const int b = bc / C, c = bc % C;
+  const float* p = x + (long)b * sb + (long)c * sc;
+  const int n = T * HW;
+  const double k = p[0];
+  double s = 0.0, q = 0.0;
+  int t = threadIdx.x / HW, hw = threadIdx.x - t * HW;
+  const int dt = 256 / HW, dhw = 256 - dt * HW;
+  for (int e = threadIdx.x; e < n; e += 256) {
+    const double d = p[(long)t * st + hw] - k;
+    s += d;
+    q += d * d;
+    t += dt; hw += dhw;
+    if (hw >= HW) { hw -= HW; ++t; }
+  }
+  __shared__ double sh[8];
+  block_sum2(s, q, sh);
+  if (threadIdx.x == 0) {
+    double mean = k + s / n, m2 = q - s * s / n;
+    if (m2 < 0) m2 = 0;
+    long cnt = n;
+    if (n_prev > 0) {
+      const double2 a = carry[bc];
+      const double na = (double)n_prev, nb = (double)n, delta = mean - a.x;
+      cnt = n_prev + n;
+      mean = a.x + delta * nb / (na + nb);
+      m2 = a.y + m2 + delta * delta * na * nb / (na + nb);
+    }
+    carry[bc] = make_double2(mean, m2);
+    const float sd = sqrtf((float)(m2 / (double)(cnt - 1)) + 1e-5f);
+    mr[bc] = make_float2((float)mean, 1.f / sd);
+    std_out[bc] = sd;
+  }
+}
+
 // one (b, c) per grid.y, 32-bit (t, hw) within it (the flat 64-bit div/mod chain dominated)
 __global__ __launch_bounds__(256) void adaptor_norm_kernel(float* d, long dsb, long dsc, long dst_, const float* s,
                                                            long ssb, long ssc, long sst, int C, int T, int HW,
@@ -972,6 +1098,27 @@ void bilinear_frames(hipStream_t s, const View& d, const View& a, const View& b,
 void adaptor_stats(hipStream_t s, const View& x, float* mean, float* std_, double* /*partials*/) {
   hipLaunchKernelGGL(adaptor_stats_kernel, dim3(x.B * x.C), dim3(256), 0, s, x.p, x.sb, x.sc, x.st, x.C, x.T, x.HW(),
                      mean, std_);
+}
+
+void adaptor_stats_inc(hipStream_t s, const View& x, long n_prev, double2* carry, float2* mr, float* std_) {
+  hipLaunchKernelGGL(adaptor_stats_inc_kernel, dim3(x.B * x.C), dim3(256), 0, s, x.p, x.sb, x.sc, x.st, x.C, x.T,
+                     x.HW(), n_prev, carry, mr, std_);
+}
+
+void channel_ln_stats(hipStream_t s, float2* out, const View& in0, const View* in1) {
+  const View& i1 = in1 ? *in1 : in0;
+  const int C = in0.C + (in1 ? in1->C : 0);
+  const long npix = (long)in0.B * in0.T * in0.HW();
+  // the float4 form by the per-sample layout alone (both forms sum a pixel in the same order)
+  auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  auto m4 = [](const View& v) { return v.sb % 4 == 0 && v.sc % 4 == 0 && v.st % 4 == 0; };
+  if (in0.HW() % 4 == 0 && a16(in0.p) && a16(i1.p) && m4(in0) && m4(i1)) {
+    hipLaunchKernelGGL(channel_ln_stats4_kernel, dim3((unsigned)((npix / 4 + 31) / 32)), dim3(256), 0, s, out, in0.p,
+                       in0.sb, in0.sc, in0.st, in0.C, i1.p, i1.sb, i1.sc, i1.st, C, in0.T, in0.HW(), in0.B);
+    return;
+  }
+  hipLaunchKernelGGL(channel_ln_stats_kernel, dim3((unsigned)((npix + 31) / 32)), dim3(256), 0, s, out, in0.p, in0.sb,
+                     in0.sc, in0.st, in0.C, i1.p, i1.sb, i1.sc, i1.st, C, in0.T, in0.HW(), in0.B);
 }
 
 void adaptor_normalize(hipStream_t s, const View& d, const View& src, const float* mean, const float* std_) {

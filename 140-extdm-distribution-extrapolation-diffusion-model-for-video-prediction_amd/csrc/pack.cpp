@@ -278,6 +278,14 @@ fvec split_channels(const fvec& w, int Co, int Cin, int kk, int lo, int hi) {
   return r;
 }
 
+fvec fold_ln_gamma(const fvec& w, const fvec& gamma, int Co, int Cin) {
+  fvec r((size_t)Co * Cin);
+  for (int m = 0; m < Co; ++m)
+    for (int c = 0; c < Cin; ++c)
+      r[(size_t)m * Cin + c] = (float)((double)w[(size_t)m * Cin + c] * (double)gamma[c]);
+  return r;
+}
+
 XPathPack pack_xpath(const fvec& wn, const fvec& bn, const fvec& wi, const fvec& bi, int Cm, int Co, int Cin, int L) {
   const int M32 = (Co + 31) / 32, MP = M32 * 32;
   // V[m][ci][a][b][e][f] = sum_c' Wa[m][c'][a][b] Wn[c'][ci][e][f]; U[m][a][b] = sum_c' Wa bn

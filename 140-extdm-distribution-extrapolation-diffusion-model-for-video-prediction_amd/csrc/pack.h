@@ -115,6 +115,10 @@ fvec pack_narrow(const fvec& w, int kk, int co, int ci, int cot);
 fvec reorder_time3(const fvec& w, int co, int ci, int kt, int kk);
 // input channels [lo, hi) of W[Co][Cin][kk]
 fvec split_channels(const fvec& w, int Co, int Cin, int kk, int lo, int hi);
+// A 1x1 conv behind a channel LayerNorm with the norm's gamma folded in: W'[co][ci] = W[co][ci] *
+// gamma[ci], the product in double (exact) rounded once to fp32; the conv then reads (x - mean) *
+// rinv (conv_x3.hip AFF = 2) and pack_x3 splits W' as any weight.
+fvec fold_ln_gamma(const fvec& w, const fvec& gamma, int Co, int Cin);
 
 // init_conv's x-branch composed with init_noise_conv (xpath_x3.hip): 49 border-class 13x13 kernels
 // over the 3 latent channels, built in fp64, packed as f16x3 A fragments [class][kstep = (ci, dy)]

@@ -729,10 +729,9 @@ struct ExtdmHandle {
       last_core = true;
       Scope sc(arena);
       const int hid = cfg.heads * cfg.dim_head;
-      View ln = alloc_cf(x.B, x.C, x.T, x.H, x.W);
-      if (!plan && bench_stage == 0) channel_ln(s, ln, x, nullptr, D(p + ".fn.norm.gamma"));
       View qkv = alloc_cf(x.B, 3 * hid, x.T, x.H, x.W);
-      if (bench_stage == 0 || bench_stage == 2) conv(qkv, ln, nullptr, P(p + ".fn.fn.attn.qkv.weight"), 1, 0, nullptr);
+      ln_conv(qkv, x, nullptr, p + ".fn.fn.attn.qkv.weight", p + ".fn.norm.gamma", nullptr, nullptr, bench_stage == 0,
+              bench_stage == 0 || bench_stage == 2);
       View o = alloc_cf(x.B, hid, x.T, x.H, x.W);
       if (!plan && (bench_stage == 0 || bench_stage == 1))
         REQUIRE(attention_core(s, qkv, o, g, cfg.heads, cfg.dim_head, bias_dense.at(p), bstride, rope_cos, rope_sin,
@@ -892,22 +891,124 @@ struct ExtdmHandle {
     return {L, ((1 << L) - 1) * tm()};
   }
 
+  // The normalisation passes ahead of a conv folded into the conv's staging (conv_x3.hip AFF).
+  // EXTDM_NO_LN_FOLD=1: the channel LayerNorm ahead of a 1x1 conv (the MotionAdaptor's predictor and
+  // fuser PreNorms, the qkv conv of the unfused STW core route) written by channel_ln again;
+  // EXTDM_NO_ADAPTOR_FOLD=1: the MotionAdaptor's extrapolators on adaptor_stats + adaptor_normalize
+  // again. Read per handle. A route is decided at its first use -- the planner's pass at max_batch,
+  // from the same checks as the launcher (conv_x3_aff_covers) -- and kept, so that the planned
+  // workspace and every forward agree; where a launch is not covered the separate passes run.
+  const bool ln_fold = !env_flag("EXTDM_NO_LN_FOLD");
+  const bool adaptor_fold = !env_flag("EXTDM_NO_ADAPTOR_FOLD");
+  std::unordered_map<std::string, bool> fold_route;
+  template <class F>
+  bool fold_on(const std::string& key, F&& covered) {
+    auto it = fold_route.find(key);
+    if (it != fold_route.end()) return it->second;
+    return fold_route[key] = covered();
+  }
+  // the 1x1 conv weight wn [Co][Cin] with the PreNorm's gamma folded in (fold_ln_gamma), packed as any weight
+  const PackedW& Pln(const std::string& wn, const std::string& gn) {
+    const std::string key = wn + "#ln";
+    if (!host.count(key)) {
+      const HostTensor& t = H(wn);
+      const int co = (int)t.shape[0], ci = (int)t.shape[1];
+      REQUIRE((int)H(gn).f.size() == ci && t.f.size() == (size_t)co * ci, "LayerNorm fold: 1x1 weight / gamma sizes: " + wn);
+      host[key] = HostTensor{fold_ln_gamma(t.f, H(gn).f, co, ci), {}, t.shape};
+    }
+    return P(key);
+  }
+  // out = conv1x1(channel LayerNorm(in0 ++ in1)) + bias + res. Folded: one statistics pass writes
+  // (mean, 1 / sqrt(var + eps)) per pixel, the conv normalises while it stages and carries gamma in
+  // its weight. norm / run: extdm_bench_layer's stages (the pass and the conv on their own).
+  void ln_conv(const View& out, const View& in0, const View* in1, const std::string& wn, const std::string& gn,
+               const float* bias, const View* res, bool norm = true, bool run = true) {
+    Scope sc(arena);
+    const bool fold = ln_fold && x3_convs() && fold_on(wn + "#ln", [&] {
+      return P(wn).wx != nullptr && conv_x3_aff_covers(out, in0, in1, P(wn), 2);
+    });
+    if (!fold) {
+      View ln = alloc_cf(out.B, in0.C + (in1 ? in1->C : 0), out.T, out.H, out.W);
+      if (!plan && norm) channel_ln(s, ln, in0, in1, D(gn));
+      if (run) conv(out, ln, nullptr, P(wn), 1, 0, bias, res);
+      return;
+    }
+    const PackedW& w = Pln(wn, gn);
+    float2* st = reinterpret_cast<float2*>(arena.alloc((size_t)2 * out.B * out.T * out.HW()));
+    const size_t sbytes = conv_x3_split_bytes(out, in0, in1, w);
+    float* ws = sbytes ? arena.alloc(sbytes / sizeof(float)) : nullptr;
+    if (plan) return;
+    if (norm) channel_ln_stats(s, st, in0, in1);
+    if (!run) return;
+    ConvEpi e;
+    e.bias = bias;
+    if (res) { e.res = res->p; e.res_sb = res->sb; e.res_sc = res->sc; e.res_st = res->st; }
+    e.split_ws = ws;
+    e.split_ws_bytes = sbytes;
+    e.in_aff_mode = 2;
+    e.in_aff = st;
+    REQUIRE(conv_x3_forward(s, out, in0, in1, w, e), "LayerNorm-folded 1x1 conv: launch not covered");
+  }
+
+  // extdm_bench_layer on a MotionAdaptor: 0 = the whole adaptor, 1 = its last extrapolator conv
+  // alone, 2 = its fuser conv alone (the other launches skipped; their buffers hold the warm-up
+  // run's values)
+  int adaptor_only = 0;
+
   // MotionAdaptor in place on frames [tm, T) of x (u12:644-717; tm = tc, or tc-1 in wo_ref)
   void adaptor(const std::string& p, const View& x) {
     Scope sc(arena);
     const int B = x.B, C = x.C, Hh = x.H, Ww = x.W, tc = tm(), tp = cfg.tp, HW = Hh * Ww;
     const AdaptorGeom ag = adaptor_geom();
     const std::string ap = p + ".adaptors";
+    const bool all = adaptor_only == 0;
     View E = alloc_tm(B, C, tc << ag.L, Hh, Ww);
     {
-      Scope s2(arena);
-      View ln = alloc_cf(B, C, tc, Hh, Ww);
       View xm = x.frames(0, tc);
-      if (!plan) channel_ln(s, ln, xm, nullptr, D(ap + ".predictor.fn.norm.gamma"));
-      conv(E.frames(0, tc), ln, nullptr, P(ap + ".predictor.fn.fn.weight"), 1, 0, D(ap + ".predictor.fn.fn.bias"),
-           &xm);
+      ln_conv(E.frames(0, tc), xm, nullptr, ap + ".predictor.fn.fn.weight", ap + ".predictor.fn.norm.gamma",
+              D(ap + ".predictor.fn.fn.bias"), &xm, all, all);
     }
-    for (int l = 0; l < ag.L; ++l) {
+    // Extrapolators, folded (every layer a (1,3,3) conv that conv_x3 covers with the per-(sample,
+    // channel) input affine): x_new = (conv(hn) + hn) std + mean with hn = (x - mean) / std is
+    // std conv(hn) + x, so the conv normalises x while it stages, scales its own term by std and adds
+    // x; hn is never written. Layer l's statistics over frames [0, nl) come from one pass over the
+    // frames layer l - 1 wrote, combined with the carried (mean, M2) of the earlier ones.
+    const bool fold = adaptor_fold && x3_convs() && fold_on(p + "#extrapolators", [&] {
+      for (int l = 0; l < ag.L; ++l) {
+        const std::string wn = ap + ".extrapolators." + std::to_string(l) + ".fn.weight";
+        const int nl = tc << l;
+        if (H(wn).shape[2] != 1 || has(ap + ".extrapolators." + std::to_string(l) + ".fn.bias") || !P(wn).wx ||
+            !conv_x3_aff_covers(E.frames(nl, nl), E.frames(0, nl), nullptr, P(wn), 1))
+          return false;
+      }
+      return true;
+    });
+    if (fold) {
+      double2* carry = reinterpret_cast<double2*>(arena.alloc((size_t)4 * B * C));
+      for (int l = 0; l < ag.L; ++l) {
+        Scope s2(arena);
+        const int nl = tc << l, nc = l ? nl / 2 : nl;  // frames written since the last statistics
+        const PackedW& w = P(ap + ".extrapolators." + std::to_string(l) + ".fn.weight");
+        float2* mr = reinterpret_cast<float2*>(arena.alloc((size_t)2 * B * C));
+        float* sd = arena.alloc((size_t)B * C);
+        const size_t sbytes = conv_x3_split_bytes(E.frames(nl, nl), E.frames(0, nl), nullptr, w);
+        float* ws = sbytes ? arena.alloc(sbytes / sizeof(float)) : nullptr;
+        if (plan) continue;
+        if (all) adaptor_stats_inc(s, E.frames(nl - nc, nc), (long)(nl - nc) * HW, carry, mr, sd);
+        if (!all && !(adaptor_only == 1 && l == ag.L - 1)) continue;
+        const View cur = E.frames(0, nl);
+        ConvEpi e;
+        e.res = cur.p; e.res_sb = cur.sb; e.res_sc = cur.sc; e.res_st = cur.st;
+        e.post_scale = sd;
+        e.post_first = 1;
+        e.split_ws = ws;
+        e.split_ws_bytes = sbytes;
+        e.in_aff_mode = 1;
+        e.in_aff = mr;
+        REQUIRE(conv_x3_forward(s, E.frames(nl, nl), cur, nullptr, w, e), "folded extrapolator conv: launch not covered");
+      }
+    }
+    for (int l = 0; l < (fold ? 0 : ag.L); ++l) {
       Scope s2(arena);
       const int nl = tc << l;
       const std::string wn = ap + ".extrapolators." + std::to_string(l) + ".fn.weight";
@@ -915,24 +1016,25 @@ struct ExtdmHandle {
       float* mean = arena.alloc((size_t)B * C);
       float* sd = arena.alloc((size_t)B * C);
       View cur = E.frames(0, nl);
-      if (!plan) adaptor_stats(s, cur, mean, sd, partials);
+      const bool run = all || (adaptor_only == 1 && l == ag.L - 1);
+      if (!plan && all) adaptor_stats(s, cur, mean, sd, partials);
       if (!t3) {
         View hn = alloc_tm(B, C, nl, Hh, Ww);
-        if (!plan) adaptor_normalize(s, hn, cur, mean, sd);
-        conv(E.frames(nl, nl), hn, nullptr, P(wn), 1, 1, nullptr, &hn, ACT_NONE, sd, mean);
+        if (!plan && all) adaptor_normalize(s, hn, cur, mean, sd);
+        if (run) conv(E.frames(nl, nl), hn, nullptr, P(wn), 1, 1, nullptr, &hn, ACT_NONE, sd, mean);
       } else {
         // Frame-major buffer with one zero frame either side: in frame-major layout
         // channel kt*C + c of frame t is channel c of frame t+kt-1, so the 3x3x3 conv
         // is a (1,3,3) conv over 3C "channels" of a plain strided view.
         View hp = alloc_tm(B, C, nl + 2, Hh, Ww);
         View hn = hp.frames(1, nl);
-        if (!plan) {
+        if (!plan && all) {
           zero_pad_frames(s, hp);
           adaptor_normalize(s, hn, cur, mean, sd);
         }
         View win = hp;
         win.C = 3 * C; win.T = nl;
-        conv(E.frames(nl, nl), win, nullptr, Ptime3(wn), 1, 1, nullptr, &hn, ACT_NONE, sd, mean);
+        if (run) conv(E.frames(nl, nl), win, nullptr, Ptime3(wn), 1, 1, nullptr, &hn, ACT_NONE, sd, mean);
       }
     }
     // Tmodulator: 1x1 conv over '(T C)' channels of the F extrapolated frames
@@ -941,12 +1043,11 @@ struct ExtdmHandle {
     View mo = alloc_tm(B, C, tp, Hh, Ww);
     View mo2 = mo;
     mo2.C = tp * C; mo2.T = 1; mo2.sc = HW; mo2.st = 0;
-    conv(mo2, ein, nullptr, P(p + ".Tmodulator.weight"), 1, 0, D(p + ".Tmodulator.bias"));
+    if (all) conv(mo2, ein, nullptr, P(p + ".Tmodulator.weight"), 1, 0, D(p + ".Tmodulator.bias"));
     // fuser: PreNorm(2C, conv1x1) on cat([xm2p, xp]) + xp
     View xp = x.frames(tc, tp);
-    View lnf = alloc_cf(B, 2 * C, tp, Hh, Ww);
-    if (!plan) channel_ln(s, lnf, mo, &xp, D(p + ".fuser.norm.gamma"));
-    conv(xp, lnf, nullptr, P(p + ".fuser.fn.weight"), 1, 0, D(p + ".fuser.fn.bias"), &xp);
+    ln_conv(xp, mo, &xp, p + ".fuser.fn.weight", p + ".fuser.norm.gamma", D(p + ".fuser.fn.bias"), &xp, all,
+            all || adaptor_only == 2);
   }
 
   // TrajWarp (u12:804-827) -> the fused pred-frame features fp' [B,256,tp,fs,fs]
@@ -2452,6 +2553,44 @@ int extdm_bench_layer(ExtdmHandle* h, int B, int layer, int iters, float* ms_out
       *ms_out = ms / iters;
       // 16 taps per output pixel (Downsample) = 4 taps per output pixel of each phase (Upsample)
       *flops_out = 2.0 * B * T * (double)(upl ? Li : Lo) * (upl ? Li : Lo) * (double)c_out * c_in * 16;
+      return;
+    }
+    // layers 20 / 21: the first MotionAdaptor of the forward as the forward issues it (run once
+    // whole, untimed): 20 = its last extrapolator conv, 21 = its fuser conv, each timed alone
+    if (layer == 20 || layer == 21) {
+      int lv = -1;
+      for (int i = 0; i < h->cfg.n_levels && lv < 0; ++i)
+        if (h->has("downs." + std::to_string(i) + ".4.adaptors.predictor.fn.fn.weight")) lv = i;
+      REQUIRE(lv >= 0, "bench layers 20-21: the model has no MotionAdaptor in its down path");
+      const std::string pre = "downs." + std::to_string(lv) + ".4";
+      const int C = h->cfg.dim * h->cfg.dim_mults[lv], Lq = L >> lv;
+      View x = h->alloc_cf(B, C, T, Lq, Lq);
+      fill_normal(s, x.p, 1, (int)x.numel(), 17, 0, 0, 1);
+      struct OnlyReset {
+        ExtdmHandle* h;
+        ~OnlyReset() { h->adaptor_only = 0; }
+      } only_reset{h};
+      h->adaptor(pre, x);  // every buffer written once
+      h->adaptor_only = layer == 20 ? 1 : 2;
+      note_kernel("");
+      h->adaptor(pre, x);  // warm
+      h->bench_kernel[layer] = noted_kernel();
+      hipEvent_t e0, e1;
+      HIPCHK(hipEventCreate(&e0));
+      HIPCHK(hipEventCreate(&e1));
+      HIPCHK(hipEventRecord(e0, s));
+      for (int i = 0; i < iters; ++i) h->adaptor(pre, x);
+      HIPCHK(hipEventRecord(e1, s));
+      HIPCHK(hipEventSynchronize(e1));
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, e0, e1));
+      (void)hipEventDestroy(e0);
+      (void)hipEventDestroy(e1);
+      *ms_out = ms / iters;
+      const AdaptorGeom ag = h->adaptor_geom();
+      const double px = (double)B * Lq * Lq;
+      *flops_out = layer == 20 ? 2.0 * px * (h->tm() << (ag.L - 1)) * (double)C * C * 9
+                               : 2.0 * px * h->cfg.tp * (double)C * 2 * C;
       return;
     }
     static const char* names[] = {"init_conv.weight", "downs.0.0.block2.proj.weight", "downs.1.0.block2.proj.weight",
