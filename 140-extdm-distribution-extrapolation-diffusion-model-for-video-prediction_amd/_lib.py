@@ -554,6 +554,7 @@ class FvdHandle:
 
 
 LPIPS_NORMALIZE, LPIPS_TRANS, LPIPS_PLAIN_MEAN = 1, 2, 4  # include/extdm.h EXTDM_LPIPS_*
+LPIPS_FP32 = 8  # EXTDM_LPIPS_FP32: this call's convolutions on the exact-fp32 kernel (csrc/lpips_f32.hip)
 LPIPS_TAPS = ('relu1', 'relu2', 'relu3', 'relu4', 'relu5')
 
 

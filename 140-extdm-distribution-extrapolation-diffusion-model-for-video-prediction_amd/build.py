@@ -16,7 +16,7 @@ REPO = os.path.dirname(HERE)
 INCLUDE = os.path.join(REPO, 'include')
 LIB = os.path.join(HERE, 'libextdm_hip.so')
 SOURCES = ['conv.hip', 'conv_halo.hip', 'conv_x3.hip', 'pw_x3.hip', 'conv_gemm_x3.hip', 'conv_narrow.hip', 'norm.hip', 'attn.hip', 'attn_core.hip', 'stw_fused.hip',
-           'stw_x3.hip', 'stw64_x3.hip', 'temporal64_x3.hip', 'cross_x3.hip', 'xpath_x3.hip', 'fea_x3.hip', 'metrics.hip', 'sampler.hip', 'decoder.hip', 'lfae.hip', 'i3d.hip', 'lpips.hip', 'i3d_f32.hip', 'pack.cpp', 'fvd.cpp', 'lpips.cpp', 'runtime.cpp']
+           'stw_x3.hip', 'stw64_x3.hip', 'temporal64_x3.hip', 'cross_x3.hip', 'xpath_x3.hip', 'fea_x3.hip', 'metrics.hip', 'sampler.hip', 'decoder.hip', 'lfae.hip', 'i3d.hip', 'lpips.hip', 'i3d_f32.hip', 'lpips_f32.hip', 'pack.cpp', 'fvd.cpp', 'lpips.cpp', 'runtime.cpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-fPIC', '-ffp-contract=off', '-I', INCLUDE, '-I', CSRC]
 # Per-file flags. The fused f16x3 attention kernels (many independent fp32 lanes of

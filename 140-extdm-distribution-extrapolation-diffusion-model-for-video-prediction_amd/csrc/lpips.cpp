@@ -2,7 +2,10 @@
 // (class LPIPS, ScalingLayer, NetLinLayer, pretrained_networks.alexnet) on a handle of its own --
 // weight registry under the package's state_dict keys, the f16x3 layout of pack_conv2d uploaded per
 // conv, a workspace planned at max_pairs x max_h x max_w, the forward as a sequence of lpips.hip
-// launches -- and the extdm_lpips_* part of the C ABI (include/extdm.h).
+// launches -- and the extdm_lpips_* part of the C ABI (include/extdm.h). A call with
+// EXTDM_LPIPS_FP32 runs the five convs on the exact-fp32 kernel of lpips_f32.hip instead (fp32
+// tiles of pack_conv2d_f32, packed and uploaded on the handle's first such call); everything
+// around the convs is shared.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -66,6 +69,11 @@ struct ExtdmLpipsHandle {
   std::vector<void*> allocations;
   bool finalized = false;
   Conv2dW conv[5];
+  // the exact-fp32 route: the conv weights as finalize packed them (the stem's with 1 / scale
+  // folded in), kept on the host until the first EXTDM_LPIPS_FP32 call uploads their fp32 tiles
+  std::vector<float> w32[5];
+  Conv2dW conv32[5];
+  bool have32 = false;
   const float* lin[5] = {};
   LpipsFront front;
   int* range = nullptr;
@@ -152,6 +160,7 @@ struct ExtdmLpipsHandle {
       w.bias = upload(b.f);
       w.M = c.M; w.Cin = c.Cin; w.Cpad = Cpad; w.KS = c.KS; w.stride = c.stride; w.pad = c.pad;
       w.bm = bm; w.nkt = p.n; w.stem = stem;
+      w32[k] = std::move(wt);
       // NetLinLayer: Conv2d(C_k, 1, 1, bias=False) behind an inference-time identity dropout
       lin[k] = upload(H("lin" + std::to_string(k) + ".model.1.weight", {1, c.M, 1, 1}).f);
     }
@@ -173,6 +182,23 @@ struct ExtdmLpipsHandle {
     finalized = true;
   }
 
+  void upload_f32() {
+    if (have32) return;
+    for (int k = 0; k < 5; ++k) {
+      const Conv2dW& c = conv[k];
+      const TilesF32 t = c.stem ? pack_conv2d_f32_stem(w32[k], c.M, c.Cin, c.KS, kLpipsF32Bm, kLpipsStemRow)
+                                : pack_conv2d_f32(w32[k], c.M, c.Cin, c.Cpad, c.KS, kLpipsF32Bm);
+      Conv2dW& w = conv32[k];
+      w = c;
+      w.bm = kLpipsF32Bm;
+      w.w = upload(t.a);
+      w.wscale = nullptr;
+      w.nkt = t.nkt;
+      std::vector<float>().swap(w32[k]);
+    }
+    have32 = true;
+  }
+
   void check_geometry(int N, int C, int Hh, int W) const {
     REQUIRE(N >= 1 && (C == 1 || C == 3), "lpips: [N][C][H][W] with C = 1 or 3 expected");
     // below 31 the second MaxPool2d(3, 2) has no output
@@ -183,13 +209,16 @@ struct ExtdmLpipsHandle {
   // relu1 .. relu(last + 1) of NI = N (in1 null) or 2 N images: set 0 in slots [0, N), set 1 in
   // [N, 2 N). The stem runs once per set (a set is one buffer); the other convs once over all.
   void run(int N, int C, int Hh, int W, const float* in0, long sn0, long sc0, const float* in1, long sn1, long sc1,
-           int pre, int last, int h[5], int w[5]) {
+           int pre, int last, bool fp32, int h[5], int w[5]) {
     tap_dims(Hh, W, h, w);
     const int NI = in1 ? 2 * N : N;
     LpipsFront f = front;
     f.pre = pre;
+    if (fp32) upload_f32();
     auto conv_ = [&](int k, const float* in, long ib, long ic, int B, int hi, int wi, float* out) {
-      REQUIRE(conv2d_x3_forward(s, in, ib, ic, B, hi, wi, conv[k], k == 0 ? &f : nullptr, out, range),
+      const LpipsFront* fr = k == 0 ? &f : nullptr;
+      REQUIRE(fp32 ? conv2d_f32_forward(s, in, ib, ic, B, hi, wi, conv32[k], fr, out)
+                   : conv2d_x3_forward(s, in, ib, ic, B, hi, wi, conv[k], fr, out, range),
               std::string("lpips: convolution ") + kConvs[k].key + " not covered (input larger than 4 GiB?)");
     };
     conv_(0, in0, sn0, C == 1 ? 0 : sc0, N, Hh, W, feat[0]);
@@ -224,7 +253,13 @@ struct ExtdmLpipsHandle {
     wH = Hh; wW = W; wplain = (int)plain;
   }
 
-  void raise_range_flag() {
+  // every entry point ends here: the stream is synchronised; on the f16x3 route the range flag is
+  // read and raised, on the fp32 route (no fp16 anywhere) it is neither written nor consulted
+  void finish(bool fp32) {
+    if (fp32) {
+      HIPCHK(hipStreamSynchronize(s));
+      return;
+    }
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, range, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -293,7 +328,8 @@ int extdm_lpips_distance(ExtdmLpipsHandle* h, int N, int C, int H, int W, const 
     tap_dims(H, W, th, tw);
     h->set_weights(H, W, th, tw, (flags & EXTDM_LPIPS_PLAIN_MEAN) != 0);
     const int pre = ((flags & EXTDM_LPIPS_NORMALIZE) ? 1 : 0) + ((flags & EXTDM_LPIPS_TRANS) ? 1 : 0);
-    h->run(N, C, H, W, in0, sn0, sc0, in1, sn1, sc1, pre, 4, th, tw);
+    const bool fp32 = (flags & EXTDM_LPIPS_FP32) != 0;
+    h->run(N, C, H, W, in0, sn0, sc0, in1, sn1, sc1, pre, 4, fp32, th, tw);
     LpipsTaps t{};
     for (int k = 0; k < 5; ++k) {
       const int hw = th[k] * tw[k];
@@ -303,7 +339,7 @@ int extdm_lpips_distance(ExtdmLpipsHandle* h, int N, int C, int H, int W, const 
     if (mean_out) lpips_mean(h->s, t, mean_out, N);
     if (map_out) lpips_map(h->s, t, map_out, N, H, W);
     HIPCHK(hipGetLastError());
-    h->raise_range_flag();
+    h->finish(fp32);
   });
 }
 
@@ -331,11 +367,12 @@ int extdm_lpips_features(ExtdmLpipsHandle* h, int N, int C, int H, int W, const 
     HIPCHK(hipMemsetAsync(h->range, 0, sizeof(int), h->s));
     const int pre = ((flags & EXTDM_LPIPS_NORMALIZE) ? 1 : 0) + ((flags & EXTDM_LPIPS_TRANS) ? 1 : 0);
     int th[5], tw[5];
-    h->run(N, C, H, W, x, sn, sc, nullptr, 0, 0, pre, tap, th, tw);
+    const bool fp32 = (flags & EXTDM_LPIPS_FP32) != 0;
+    h->run(N, C, H, W, x, sn, sc, nullptr, 0, 0, pre, tap, fp32, th, tw);
     HIPCHK(hipMemcpyAsync(out, h->feat[tap], (size_t)N * kConvs[tap].M * th[tap] * tw[tap] * sizeof(float),
                           hipMemcpyDeviceToDevice, h->s));
     HIPCHK(hipGetLastError());
-    h->raise_range_flag();
+    h->finish(fp32);
   });
 }
 

@@ -1,4 +1,4 @@
-// LPIPS (AlexNet, version 0.1) -- kernels of lpips.hip.
+// LPIPS (AlexNet, version 0.1) -- kernels of lpips.hip and lpips_f32.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,7 +11,9 @@ inline int conv2d_out(int size, int k, int stride, int pad) {
 inline int pool32_out(int size) { return size < 3 ? 0 : (size - 3) / 2 + 1; }
 
 // f16x3 packing of a Conv2d weight [M][Cin][KS][KS] (pack_conv2d): tap-major K, or the 3-channel
-// 11x11 stem's ky-row layout (stem: k = ky * 40 + kx * 3 + ci, K = 440).
+// 11x11 stem's ky-row layout (stem: k = ky * 40 + kx * 3 + ci, K = 440). The exact-fp32 route
+// (lpips_f32.hip) describes its fp32 tiles (pack_conv2d_f32, the same k order) with the same
+// struct: w the float tiles, wscale null.
 struct Conv2dW {
   const void* w = nullptr;
   const float* wscale = nullptr;
@@ -21,6 +23,10 @@ struct Conv2dW {
 };
 constexpr int kLpipsStemRow = 40;  // 11 kx * 3 ci = 33 elements of a ky row, padded to five groups of 8
 inline int conv2d_bm(int M) { return M >= 128 ? 128 : 64; }
+// The exact-fp32 route's m-tile, for every Cout: the 128-row tile holds two accumulator sets
+// (partial and total, 290 registers a lane) and runs one workgroup per CU; 64 rows run three, and
+// 4096 pairs of 64 x 64 take 2.15 us per pair instead of 3.02 (Cout 192 is three full tiles).
+constexpr int kLpipsF32Bm = 64;
 
 // The stem's front end, applied while gathering: `pre` times v <- v * 2 - 1 (trans of
 // calculate_lpips.py:15-23 and / or LPIPS.forward's normalize), then the ScalingLayer's v - shift[ci];
@@ -36,6 +42,11 @@ struct LpipsFront {
 // front: non-null for the stem only. False if the launch is not covered (offsets past 32 bits).
 bool conv2d_x3_forward(hipStream_t s, const float* in, long ib, long ic, int B, int Hi, int Wi, const Conv2dW& w,
                        const LpipsFront* front, float* out, int* range);
+
+// The same convolution on the exact-fp32 route (lpips_f32.hip, v_mfma_f32_32x32x2_f32): w the fp32
+// tiles of pack_conv2d_f32 / pack_conv2d_f32_stem (wscale null). No range flag.
+bool conv2d_f32_forward(hipStream_t s, const float* in, long ib, long ic, int B, int Hi, int Wi, const Conv2dW& w,
+                        const LpipsFront* front, float* out);
 
 // MaxPool2d(3, 2), no padding, floor: contiguous [B * C][H][W] -> [B * C][(H-3)/2+1][(W-3)/2+1]
 void maxpool2d_32(hipStream_t s, const float* in, float* out, long planes, int H, int W);

@@ -156,6 +156,12 @@ TilesF32 pack_conv3d_f32(const fvec& w, int M, int Cin, int Cpad, int KS, int bm
 TilesF32 pack_conv3d_f32_stem(const fvec& w, int M, int Cin, int KS, int bm, int stem_row) {
   return stem_tiles_f32(w, M, Cin, KS, KS * KS * KS, KS * KS, bm, stem_row);
 }
+TilesF32 pack_conv2d_f32(const fvec& w, int M, int Cin, int Cpad, int KS, int bm) {
+  return tap_major_f32(w, M, Cin, Cpad, KS * KS, bm);
+}
+TilesF32 pack_conv2d_f32_stem(const fvec& w, int M, int Cin, int KS, int bm, int stem_row) {
+  return stem_tiles_f32(w, M, Cin, KS, KS * KS, KS, bm, stem_row);
+}
 
 Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng) {
   const int kk = ks * ks, cib = 16 * ng, ncgb = (ci + cib - 1) / cib, mt = (co + bm - 1) / bm;

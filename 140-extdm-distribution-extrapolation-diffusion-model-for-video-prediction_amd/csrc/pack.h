@@ -1,7 +1,8 @@
 // Weight layouts of the MFMA / VALU kernels as pure host functions (no HIP, no kernels.h): host
 // vectors and the tile parameters the kernel files choose in, host vectors out. runtime.cpp,
 // fvd.cpp and lpips.cpp upload the results; tests/pack_driver.cpp, tests/pack_lpips_driver.cpp,
-// tests/pack_updown_driver.cpp and tests/pack_f32_driver.cpp run the same functions on the CPU.
+// tests/pack_updown_driver.cpp, tests/pack_f32_driver.cpp and tests/pack_lpips_f32_driver.cpp run
+// the same functions on the CPU.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -79,7 +80,7 @@ Frags pack_unit3d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int s
 // KS kx * Cin ci elements (j = kx * Cin + ci) padded to stem_row, k = ky * stem_row + j,
 // K = KS * stem_row (AlexNet's 11x11: 33 of 40, K = 440)
 Frags pack_conv2d(const fvec& w, int M, int Cin, int Cpad, int KS, int bm, int stem_row);
-// fp32 tile layout of InceptionI3d's exact-fp32 convolution (i3d_f32.hip):
+// fp32 tile layout of the exact-fp32 convolutions (f32_tiles.h: i3d_f32.hip, lpips_f32.hip):
 // a[((mtile * nkt + ktile) * 32 + r) * bm + c] = element (row m = mtile*bm + c, k = ktile*32 + r) of
 // the dense [M][K] matrix, nkt = ceil(K / 32), ceil(M / bm) m-tiles; 0 for m >= M, k >= K and where
 // the matrix has no element (pad channels, the stem rows' pad columns). No scaling.
@@ -90,6 +91,13 @@ TilesF32 pack_conv3d_f32(const fvec& w, int M, int Cin, int Cpad, int KS, int bm
 // its stem variant: (kt, ky) rows of KS kx * Cin ci elements (j = kx * Cin + ci) padded to stem_row,
 // k = (kt*KS + ky) * stem_row + j, K = KS*KS*stem_row (the 3-channel 7x7x7 unit: 21 of 24, K = 1176)
 TilesF32 pack_conv3d_f32_stem(const fvec& w, int M, int Cin, int KS, int bm, int stem_row);
+// Conv2d weight [M][Cin][KS][KS] for conv2d_f32_kernel (lpips_f32.hip): k = tap * Cpad + ci,
+// tap = ky*KS + kx (channels ci >= Cin zero), K = KS^2 * Cpad; element (m, k) = w[m][ci][ky][kx]
+TilesF32 pack_conv2d_f32(const fvec& w, int M, int Cin, int Cpad, int KS, int bm);
+// its stem variant: ky rows of KS kx * Cin ci elements (j = kx * Cin + ci) padded to stem_row,
+// k = ky * stem_row + j, K = KS * stem_row; element (m, k) = w[m][j % Cin][ky][j / Cin] for
+// j < KS * Cin, zero for the pad columns (AlexNet's 3-channel 11x11: 33 of 40, K = 440)
+TilesF32 pack_conv2d_f32_stem(const fvec& w, int M, int Cin, int KS, int bm, int stem_row);
 // f16x3 layout (conv_x3.hip): [mtile][cb*KS + ky][(g, kx)][m32][hi|lo][lane][8], lane = (h, lc): row
 // m = mtile*BM + m32*32 + lc, input channel cb*16NG + g*16 + 8h + e. Rows scaled as in pack_frags.
 Frags pack_x3(const fvec& w, int ks, int co, int ci, int bm, int ng);

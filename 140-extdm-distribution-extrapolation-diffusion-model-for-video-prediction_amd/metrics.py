@@ -236,10 +236,11 @@ def _need_rocm(x):
 
 
 class _MetricPrecision:
-    """The `precision` attribute of InceptionI3d: 'f16x3' (the default), 'fp32' (the
+    """The `precision` attribute of InceptionI3d and LPIPS: 'f16x3' (the default), 'fp32' (the
     exact-fp32 convolutions on v_mfma_f32_32x32x2_f32, no fp16 range limit) or 'auto': f16x3 until
     the library reports an activation at the fp16 range, then one RuntimeWarning, the call re-run
-    on a handle rebuilt for fp32, and fp32 from then on (GaussianDiffusion._run_sampler's scheme)."""
+    on fp32 (InceptionI3d: on a handle rebuilt for it; LPIPS: on the same handle, the route is a
+    flag of the call), and fp32 from then on (GaussianDiffusion._run_sampler's scheme)."""
 
     PRECISIONS = ('f16x3', 'fp32', 'auto')
     _RANGE_MSG = 'out of fp16 range (|v| >= 65504)'
@@ -513,7 +514,7 @@ class _NetLinLayer(nn.Module):
         self.model = nn.Sequential(nn.Dropout(), nn.Conv2d(chn_in, 1, 1, stride=1, padding=0, bias=False))
 
 
-class LPIPS(nn.Module):
+class LPIPS(_MetricPrecision, nn.Module):
     """lpips.LPIPS(net='alex', version='0.1', lpips=True), the metric of
     metrics/calculate_lpips.py:12, on the native library. The `lpips` package is not part of the
     reference, so the network is restated from the published package: the package's
@@ -523,7 +524,9 @@ class LPIPS(nn.Module):
     `pretrained=True` loads nothing (there is no file to load): weights come from load_state_dict
     or load_lpips_pretrained. Inference only; inputs are [N, 1 or 3, H >= 31, W >= 31] device
     tensors in [-1, 1] ([0, 1] with normalize=True). A pair's value is bitwise independent of the
-    batch it sits in."""
+    batch it sits in. `precision` (an attribute, _MetricPrecision; not a constructor parameter and
+    not in the state_dict) selects the arithmetic of the five convolutions per call through
+    EXTDM_LPIPS_FP32; both routes share one native handle."""
 
     def __init__(self, pretrained=True, net='alex', version='0.1', lpips=True, spatial=False, pnet_rand=False,
                  pnet_tune=False, use_dropout=True, model_path=None, eval_mode=True, verbose=True):
@@ -591,11 +594,15 @@ class LPIPS(nn.Module):
         smap = torch.empty(N, H, W, device=in0.device) if want_map else None
         step = max(1, int(self.chunk))
         h = self._h(in0.device, min(N, step), H, W)
-        with torch.cuda.device(in0.device):
-            for i in range(0, N, step):
-                j = min(N, i + step)
-                h.distance(in0[i:j], in1[i:j], flags, mean[i:j] if want_mean else None,
-                           smap[i:j] if want_map else None)
+
+        def run():
+            f = flags | (_lib.LPIPS_FP32 if self._route() == 'fp32' else 0)
+            with torch.cuda.device(in0.device):
+                for i in range(0, N, step):
+                    j = min(N, i + step)
+                    h.distance(in0[i:j], in1[i:j], f, mean[i:j] if want_mean else None,
+                               smap[i:j] if want_map else None)
+        self._on_route(run)
         return mean, smap
 
     def forward(self, in0, in1, retPerLayer=False, normalize=False):
@@ -615,8 +622,12 @@ class LPIPS(nn.Module):
         k = _lib.LPIPS_TAPS.index(tap) if isinstance(tap, str) else int(tap)
         N, _, H, W = x.shape
         h = self._h(x.device, (N + 1) // 2, H, W)
-        with torch.cuda.device(x.device):
-            return h.features(x, k, _lib.LPIPS_NORMALIZE if normalize else 0)
+
+        def run():
+            f = (_lib.LPIPS_NORMALIZE if normalize else 0) | (_lib.LPIPS_FP32 if self._route() == 'fp32' else 0)
+            with torch.cuda.device(x.device):
+                return h.features(x, k, f)
+        return self._on_route(run)
 
 
 def load_lpips_pretrained(device, alexnet_path, lin_path):

@@ -350,7 +350,9 @@ int extdm_fvd_range_flag(ExtdmFvdHandle* h, int reset, void* stream);
  * `net.slice5.10` with `.weight` / `.bias`, and `linK.model.1.weight` [1][C_K][1][1], K = 0 .. 4;
  * `lins.K.model.1.weight` is accepted as an alias of `linK...` and must equal it if both are given.
  * extdm_lpips_finalize packs the convs for the f16x3 2-D convolution and allocates the workspace for
- * max_pairs pairs of max_h x max_w images; a missing key is an error naming the key. */
+ * max_pairs pairs of max_h x max_w images; a missing key is an error naming the key. The fp32
+ * tiles of the exact-fp32 route are packed and uploaded by the handle's first call with
+ * EXTDM_LPIPS_FP32 (about 10 MB); a handle that never sees the flag allocates nothing for it. */
 typedef struct ExtdmLpipsHandle ExtdmLpipsHandle;
 int extdm_lpips_create(int max_pairs, int max_h, int max_w, int device, ExtdmLpipsHandle** out);
 void extdm_lpips_destroy(ExtdmLpipsHandle* h);
@@ -362,6 +364,10 @@ int extdm_lpips_finalize(ExtdmLpipsHandle* h);
 #define EXTDM_LPIPS_NORMALIZE 1  /* LPIPS.forward(normalize=True): x * 2 - 1 first */
 #define EXTDM_LPIPS_TRANS 2      /* trans (calculate_lpips.py:15-23): x * 2 - 1 first */
 #define EXTDM_LPIPS_PLAIN_MEAN 4 /* mean_out as LPIPS(spatial=False): spatial_average of each lin map */
+/* The five convolutions of this call in exact fp32 on v_mfma_f32_32x32x2_f32 instead of f16x3: no
+ * fp16 range limit, so the range flag is neither raised nor consulted and stays 0. The pools, the
+ * distance head, the mean and the map are the same launches on both routes. */
+#define EXTDM_LPIPS_FP32 8
 
 /* LPIPS.forward(in0, in1) for N pairs in one batch (replaces the one-pair-per-forward loops of
  * calculate_lpips.py:40-60, 83-93, 102-112, 122-132): in0, in1 [N][C][H][W] through the element
@@ -371,14 +377,16 @@ int extdm_lpips_finalize(ExtdmLpipsHandle* h);
  * EXTDM_LPIPS_PLAIN_MEAN the spatial=False value instead. map_out [N][H][W]: the spatial=True map
  * (bilinear upsample, align_corners=False, of the five lin maps, summed). Either may be NULL. Errors
  * on H or W < 31 (the second MaxPool2d(3, 2) has no output), N > max_pairs, H > max_h or W > max_w.
- * A pair's values do not depend on the batch it sits in. Fails if an f16x3 convolution input
- * reached |v| >= 65504 (the sticky range flag, reset at entry). Synchronises the stream. */
+ * A pair's values do not depend on the batch it sits in, on either route. Without
+ * EXTDM_LPIPS_FP32 the call fails if an f16x3 convolution input reached |v| >= 65504 (the sticky
+ * range flag, reset at entry). Synchronises the stream. */
 int extdm_lpips_distance(ExtdmLpipsHandle* h, int N, int C, int H, int W, const float* in0, long sn0, long sc0,
                          const float* in1, long sn1, long sc1, int flags, float* mean_out, float* map_out,
                          void* stream);
 
 /* The parity hook: tap 0 .. 4 = relu1 .. relu5 of pretrained_networks.alexnet.forward for one image
- * set x [N][C][H][W] (N <= 2 max_pairs), post-ReLU and un-normalised, into out [N][C'][h][w];
+ * set x [N][C][H][W] (N <= 2 max_pairs), post-ReLU and un-normalised, into out [N][C'][h][w], on
+ * the f16x3 route or, with EXTDM_LPIPS_FP32, the exact-fp32 one;
  * extdm_lpips_feature_shape writes dims = {C', h, w} (no device needed; 0 extents where the input
  * is too small). */
 int extdm_lpips_features(ExtdmLpipsHandle* h, int N, int C, int H, int W, const float* x, long sn, long sc, int flags,
@@ -394,7 +402,8 @@ int extdm_lpips_maxpool(const float* x, int B, int C, int H, int W, float* out, 
  * from `in` to `out` samples, in fp64; they sum to 1. A host function, no device. -1: bad argument. */
 int extdm_lpips_mean_weights(int in, int out, double* w);
 
-/* 1 if a convolution input of this handle reached |v| >= 65504 since the last reset. */
+/* 1 if an f16x3 convolution input of this handle reached |v| >= 65504 since the last reset (calls
+ * with EXTDM_LPIPS_FP32 leave it 0). */
 int extdm_lpips_range_flag(ExtdmLpipsHandle* h, int reset, void* stream);
 
 #ifdef __cplusplus
