@@ -13,7 +13,7 @@ EXPORTS = ['extdm_create', 'extdm_destroy', 'extdm_last_error', 'extdm_load_weig
            'extdm_decode', 'extdm_set_lfae', 'extdm_region_params', 'extdm_region_hw', 'extdm_bg_params',
            'extdm_flow_predict', 'extdm_flow_hw', 'extdm_bottleneck', 'extdm_range_flag',
            'extdm_attn_layer', 'extdm_frame_metrics_workspace', 'extdm_frame_metrics', 'extdm_bilinear_frames',
-           'extdm_sampler_step_t', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum',
+           'extdm_sampler_step_t', 'extdm_sampler_step_hist', 'extdm_q_sample', 'extdm_p_losses', 'extdm_abs_diff_chunks', 'extdm_abs_diff_sum',
            'extdm_fvd_create', 'extdm_fvd_destroy', 'extdm_fvd_load_weight', 'extdm_fvd_finalize',
            'extdm_fvd_preprocess', 'extdm_fvd_features', 'extdm_fvd_endpoint', 'extdm_fvd_endpoint_shape',
            'extdm_fvd_range_flag', 'extdm_fvd_same_pad', 'extdm_fvd_maxpool', 'extdm_fvd_set_precision',
@@ -28,6 +28,7 @@ BG_TYPES = {'zero': 0, 'shift': 1, 'affine': 2, 'perspective': 3}
 
 SAMPLER_DDPM = 0
 SAMPLER_DDIM = 1
+SAMPLER_DPMPP = 2  # DPM-Solver++(2M)
 LOSS_TYPES = {'l1': 0, 'l2': 1}  # include/extdm.h EXTDM_LOSS_*
 
 # include/extdm.h EXTDM_PRECISION_*: arithmetic of the direct convolutions
@@ -122,6 +123,8 @@ def load():
     L.extdm_bilinear_frames.restype = i32
     L.extdm_sampler_step_t.argtypes = [vp, i32, i32, vp, vp, f32, vp, vp, vp, vp, vp]
     L.extdm_sampler_step_t.restype = i32
+    L.extdm_sampler_step_hist.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    L.extdm_sampler_step_hist.restype = i32
     L.extdm_q_sample.argtypes = [vp, i32, vp, vp, vp, u64, i32, i32, vp, vp, vp]
     L.extdm_q_sample.restype = i32
     L.extdm_x0_loss.argtypes = [vp, i32, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
@@ -350,6 +353,13 @@ class Handle:
         _require_device(x, eps, noise, thresh_out)
         check(load().extdm_sampler_step(self.h, x.shape[0], sampler, int(t), int(t_next), float(eta), _ptr(x),
                                         _ptr(eps), _ptr(noise), _ptr(thresh_out), _stream()))
+
+    def sampler_step_hist(self, t_prev, t, t_next, x, eps, x0_prev, thresh_out=None):
+        """One DPM-Solver++(2M) update in place on x and x0_prev (t_prev < 0: first step, t_next < 0:
+        final step)."""
+        _require_device(x, eps, x0_prev, thresh_out)
+        check(load().extdm_sampler_step_hist(self.h, x.shape[0], int(t_prev), int(t), int(t_next), _ptr(x), _ptr(eps),
+                                             _ptr(x0_prev), _ptr(thresh_out), _stream()))
 
     # ---- teacher-forced evaluation step (include/extdm.h); every t is a device int64 [B] ----
     def sampler_step_t(self, sampler, t, t_next, eta, x, eps, noise=None, thresh_out=None):

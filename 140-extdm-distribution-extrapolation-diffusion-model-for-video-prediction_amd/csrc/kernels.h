@@ -469,7 +469,10 @@ struct StepCoef {  // per sampler step (host-computed in fp32 exactly like the r
   float c1, c2, sigma;        // DDPM: posterior coef1/coef2, exp(0.5*logvar)*[t!=0]; DDIM: sqrt(a_next), c, sigma
   int t;                      // model timestep
   int use_noise;              // 0 => no noise term (DDIM time_next == 0)
-  int kind;                   // 0 = DDPM, 1 = DDIM
+  int kind;                   // 0 = DDPM, 1 = DDIM, 2 = DPM-Solver++(2M)
+  // kind 2 (host fp64, rounded once): c1 = c0 (on x0), c2 = sigma_next / sigma (on x), c3 = cp (on the
+  // previous step's x0); x = (c2 x + c1 x0) + c3 x0_prev. Unused by kinds 0 and 1.
+  float c3;
 };
 void sampler_step(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs,
                   const int* step_ctr, const float* noise /*[S][B][n] or null*/, uint64_t seed, int sample_base,
@@ -484,6 +487,13 @@ size_t sampler_sel_bytes(int B, int n);
 void sampler_step_mw(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs, int* step_ctr,
                      const float* noise, uint64_t seed, int sample_base, int round, int k_lo, int k_hi, float q_w,
                      float* thresh_out, unsigned* ws, int* t_next, int nsteps);
+// The DPM-Solver++(2M) step (kind 2) in both forms: the same threshold, then x = (c2 x + c1 x0) +
+// c3 x0_prev and x0_prev = the thresholded x0, in place. x0_prev: [B][n]. No noise term.
+void sampler_step_hist(hipStream_t s, float* x, const float* eps, float* x0_prev, int B, int n, const StepCoef* coefs,
+                       const int* step_ctr, int k_lo, int k_hi, float q_w, float* thresh_out);
+void sampler_step_hist_mw(hipStream_t s, float* x, const float* eps, float* x0_prev, int B, int n,
+                          const StepCoef* coefs, int* step_ctr, int k_lo, int k_hi, float q_w, float* thresh_out,
+                          unsigned* ws, int* t_next, int nsteps);
 // Per-sample-coefficient forms (sampler.hip): coefs[b] is sample b's StepCoef.
 // sampler_step_t: the multi-workgroup update with noise [B][n] indexed like step 0 of a shared-t call.
 void sampler_step_t(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs, const float* noise,

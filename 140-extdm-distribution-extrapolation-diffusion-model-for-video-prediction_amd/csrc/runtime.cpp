@@ -116,6 +116,9 @@ struct ExtdmHandle {
   StepCoef* coefs = nullptr;
   int coefs_cap = 0;
   float* eps_buf = nullptr;
+  // DPM-Solver++(2M): the previous step's thresholded x0, [max_batch][n]; allocated by the first
+  // extdm_sample call with EXTDM_SAMPLER_DPMPP (ensure_x0_prev), cleared at the start of each
+  float* x0_prev = nullptr;
   // teacher-forced step (extdm_q_sample / extdm_x0_loss / extdm_p_losses / extdm_sampler_step_t):
   // per-sample q_sample coefficients, loss partials [max_batch][loss_chunks(n)], and extdm_p_losses'
   // x_t / drawn-noise buffers ([max_batch][n] each, allocated with the rest in finalize_workspace)
@@ -1908,6 +1911,50 @@ struct ExtdmHandle {
     return c;
   }
 
+  void ensure_x0_prev() {
+    if (x0_prev) return;
+    const size_t n = (size_t)3 * cfg.tp * cfg.latent * cfg.latent;
+    x0_prev = dmalloc((size_t)std::max(cfg.max_batch, 1) * n * sizeof(float));
+  }
+
+  // DPM-Solver++(2M) (data prediction, multistep; Lu et al. 2022) from t towards t_next, t_prev the
+  // step before (t_prev > t > t_next). With abar = alphas_cumprod[.], alpha = sqrt(abar), sigma =
+  // sqrt(1 - abar), lambda = log(alpha / sigma), h = lambda(t_next) - lambda(t), r = (lambda(t) -
+  // lambda(t_prev)) / h and a = alpha(t_next) (1 - exp(-h)):
+  //   x = (sigma(t_next) / sigma(t)) x + a (1 + 1 / (2 r)) x0 - a / (2 r) x0_prev
+  // t_prev < 0: the first-order start (x0 weight a, no history term); t_next < 0: the final step to
+  // the clean sample, x = x0. fp64 (expm1) on the handle's fp32 schedule buffers, rounded once.
+  StepCoef make_coef_dpmpp(int t_prev, int t, int t_next) {
+    REQUIRE(t >= 0 && t < cfg.timesteps && t_prev < cfg.timesteps && t_next < t && (t_prev < 0 || t_prev > t),
+            "dpmpp: timesteps must be strictly decreasing inside [0, timesteps)");
+    StepCoef c{};
+    c.t = t;
+    c.kind = 2;
+    c.sra = H("sqrt_recip_alphas_cumprod").f.at(t);
+    c.srm1 = H("sqrt_recipm1_alphas_cumprod").f.at(t);
+    if (t_next < 0) {
+      c.c1 = 1.f;
+      return c;
+    }
+    const auto& acp = H("alphas_cumprod").f;
+    auto alpha = [&](int i) { return std::sqrt((double)acp.at(i)); };
+    auto sigma = [&](int i) { return std::sqrt(1.0 - (double)acp.at(i)); };
+    auto lambda = [&](int i) { return std::log(alpha(i) / sigma(i)); };
+    REQUIRE(sigma(t) > 0.0 && sigma(t_next) > 0.0, "dpmpp: alphas_cumprod reaches 1");
+    const double h = lambda(t_next) - lambda(t);
+    const double a = -alpha(t_next) * std::expm1(-h);
+    double c0 = a, cp = 0.0;
+    if (t_prev >= 0) {
+      const double r = (lambda(t) - lambda(t_prev)) / h;
+      c0 = a * (1.0 + 1.0 / (2.0 * r));
+      cp = -a / (2.0 * r);
+    }
+    c.c1 = (float)c0;
+    c.c2 = (float)(sigma(t_next) / sigma(t));
+    c.c3 = (float)cp;
+    return c;
+  }
+
   // The per-sample tables of a device t vector (int64 [B]): with `step`, coefs[b] = make_coef(t_b[,
   // t_next_b]); with `qs`, qs_coefs[b] = (sqrt_alphas_cumprod[t_b], sqrt_one_minus_alphas_cumprod[t_b]).
   // Reads t back (synchronises `st`) so that the fp32 expressions stay the host's.
@@ -2074,6 +2121,8 @@ int extdm_sampler_step(ExtdmHandle* h, int B, int sampler, int t, int t_next, fl
   return guarded([&] {
     REQUIRE(h && h->finalized, "handle not finalized");
     REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(sampler != EXTDM_SAMPLER_DPMPP,
+            "sampler_step: EXTDM_SAMPLER_DPMPP carries the previous step's x0; use extdm_sampler_step_hist");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
     h->ensure_coefs(1);
@@ -2094,12 +2143,40 @@ int extdm_sampler_step(ExtdmHandle* h, int B, int sampler, int t, int t_next, fl
   });
 }
 
+int extdm_sampler_step_hist(ExtdmHandle* h, int B, int t_prev, int t, int t_next, float* x, const float* eps,
+                            float* x0_prev, float* thresh_out, void* stream) {
+  return guarded([&] {
+    REQUIRE(h && h->finalized, "handle not finalized");
+    REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
+    REQUIRE(x && eps && x0_prev, "sampler_step_hist: null pointer");
+    HIPCHK(hipSetDevice(h->cfg.device));
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    h->ensure_coefs(1);
+    StepCoef c = h->make_coef_dpmpp(t_prev, t, t_next);
+    HIPCHK(hipMemcpyAsync(h->coefs, &c, sizeof(c), hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemsetAsync(h->step_ctr, 0, sizeof(int), s));
+    const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    int klo, khi;
+    float w;
+    h->quantile_ranks(n, klo, khi, w);
+    if (ExtdmHandle::sampler_mw()) {
+      sampler_step_hist_mw(s, x, eps, x0_prev, B, n, h->coefs, h->step_ctr, klo, khi, w, thresh_out, h->sel, nullptr,
+                           1);
+    } else {
+      sampler_step_hist(s, x, eps, x0_prev, B, n, h->coefs, h->step_ctr, klo, khi, w, thresh_out);
+    }
+    HIPCHK(hipStreamSynchronize(s));  // `c` is a host temporary
+  });
+}
+
 int extdm_sampler_step_t(ExtdmHandle* h, int B, int sampler, const int64_t* t, const int64_t* t_next, float eta,
                          float* x, const float* eps, const float* noise, float* thresh_out, void* stream) {
   return guarded([&] {
     REQUIRE(h && h->finalized, "handle not finalized");
     REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
     REQUIRE(t && x && eps, "sampler_step_t: null pointer");
+    REQUIRE(sampler != EXTDM_SAMPLER_DPMPP,
+            "sampler_step_t: EXTDM_SAMPLER_DPMPP is a multistep solver and has no per-sample-t form");
     REQUIRE(sampler == EXTDM_SAMPLER_DDPM || t_next, "sampler_step_t: DDIM needs t_next");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2198,6 +2275,8 @@ int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, co
     REQUIRE(h && h->finalized, "handle not finalized");
     REQUIRE(B >= 1 && B <= h->cfg.max_batch, "batch exceeds max_batch");
     REQUIRE(S >= 1 && times, "empty schedule");
+    const bool dpmpp = sampler == EXTDM_SAMPLER_DPMPP;
+    REQUIRE(!dpmpp || !noise, "sample: EXTDM_SAMPLER_DPMPP is deterministic and takes no noise");
     HIPCHK(hipSetDevice(h->cfg.device));
     hipStream_t caller = reinterpret_cast<hipStream_t>(stream);
     hipStream_t s = h->work;
@@ -2207,9 +2286,17 @@ int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, co
     HIPCHK(hipStreamWaitEvent(s, h->ev_in, 0));
     h->ensure_coefs(S);
     std::vector<StepCoef> cs(S);
-    for (int k = 0; k < S; ++k) cs[k] = h->make_coef(sampler, times[k], times_next ? times_next[k] : 0, eta);
+    for (int k = 0; k < S; ++k) {
+      // DPM-Solver++(2M): from times[k] towards times[k + 1] (the last step: to the clean sample)
+      cs[k] = dpmpp ? h->make_coef_dpmpp(k > 0 ? times[k - 1] : -1, times[k], k + 1 < S ? times[k + 1] : -1)
+                    : h->make_coef(sampler, times[k], times_next ? times_next[k] : 0, eta);
+    }
     HIPCHK(hipMemcpyAsync(h->coefs, cs.data(), S * sizeof(StepCoef), hipMemcpyHostToDevice, s));
     const int n = 3 * h->cfg.tp * h->cfg.latent * h->cfg.latent;
+    if (dpmpp) {
+      h->ensure_x0_prev();
+      HIPCHK(hipMemsetAsync(h->x0_prev, 0, (size_t)B * n * sizeof(float), s));
+    }
     if (x_T) HIPCHK(hipMemcpyAsync(out, x_T, (size_t)B * n * sizeof(float), hipMemcpyDeviceToDevice, s));
     else fill_normal(s, out, B, n, seed, sample_base, round, 0x7FFFFFFF);
     HIPCHK(hipMemsetAsync(h->step_ctr, 0, sizeof(int), s));
@@ -2229,7 +2316,15 @@ int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, co
     auto step = [&]() {
       if (!mw) set_t_from_step(s, h->t_batch, B, h->coefs, h->step_ctr);
       h->unet_step(B, out, cond_fea, h->eps_buf);
-      if (mw) {
+      if (dpmpp) {
+        if (mw) {
+          sampler_step_hist_mw(s, out, h->eps_buf, h->x0_prev, B, n, h->coefs, h->step_ctr, klo, khi, w, thr, h->sel,
+                               h->t_batch, S);
+        } else {
+          sampler_step_hist(s, out, h->eps_buf, h->x0_prev, B, n, h->coefs, h->step_ctr, klo, khi, w, thr);
+          incr_counter(s, h->step_ctr);
+        }
+      } else if (mw) {
         sampler_step_mw(s, out, h->eps_buf, B, n, h->coefs, h->step_ctr, noise, seed, sample_base, round, klo, khi,
                         w, thr, h->sel, h->t_batch, S);
       } else {

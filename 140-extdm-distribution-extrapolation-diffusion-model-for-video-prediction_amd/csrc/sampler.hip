@@ -6,6 +6,10 @@
 //   x0  = clamp(x0, -s, s) / s
 //   DDPM: x = c1 x0 + c2 x + sigma * noise                     (Diffusion.py:136-177)
 //   DDIM: x = sqrt(a_next) x0 + c eps + sigma * noise          (Diffusion.py:220-255)
+//   DPM-Solver++(2M) (the HIST instantiations; Lu et al. 2022, not in the reference):
+//         x = (c2 x + c1 x0) + c3 x0_prev, evaluated in that order — three fp32 products, the
+//         x and x0 terms added first, the history term last (contraction is off); then
+//         x0_prev = x0, the thresholded value, written by the thread that read it. No noise.
 // Coefficients come from a per-step table the host fills in fp32 with the
 // reference's own expressions; the current step index lives in device memory so
 // a captured hipGraph of one denoising step can be replayed for the whole loop.
@@ -121,11 +125,14 @@ __device__ float radix_select(const float* xb, const float* eb, const StepCoef& 
   return __uint_as_float(prefix);
 }
 
+// HIST: the DPM-Solver++(2M) update with the history buffer x0_prev [B][n] (read, then overwritten
+// in place by the same thread); coefs[step] has kind 2. !HIST: DDPM / DDIM, x0_prev is not touched.
+template <bool HIST>
 __global__ __launch_bounds__(1024) void sampler_step_kernel(float* x, const float* eps, int n,
                                                             const StepCoef* coefs, const int* step_ctr,
                                                             const float* noise, int B, uint64_t seed,
                                                             int sample_base, int round, int k_lo, int k_hi,
-                                                            float q_w, float* thresh_out) {
+                                                            float q_w, float* thresh_out, float* x0_prev) {
   __shared__ unsigned hist[256];
   __shared__ unsigned sh[2];
   const int b = blockIdx.x;
@@ -139,6 +146,17 @@ __global__ __launch_bounds__(1024) void sampler_step_kernel(float* x, const floa
   float s = q_w < 0.5f ? vlo + q_w * (vhi - vlo) : vhi - (vhi - vlo) * (1.f - q_w);
   if (s < 1.f) s = 1.f;
   if (thresh_out && threadIdx.x == 0) thresh_out[(size_t)step * B + b] = s;
+  if (HIST) {
+    float* pb = x0_prev + (long)b * n;
+    for (int e = threadIdx.x; e < n; e += blockDim.x) {
+      const float xv = xb[e], ev = eb[e];
+      const float x0 = c.sra * xv - c.srm1 * ev;
+      const float xc = fminf(fmaxf(x0, -s), s) / s;
+      xb[e] = (c.c2 * xv + c.c1 * xc) + c.c3 * pb[e];
+      pb[e] = xc;
+    }
+    return;
+  }
   const float* nb = noise ? noise + ((long)step * B + b) * n : nullptr;
   for (int e = threadIdx.x; e < n; e += blockDim.x) {
     const float xv = xb[e], ev = eb[e];
@@ -281,11 +299,14 @@ __global__ __launch_bounds__(SNT) void radix_count_kernel(const float* x, const 
 
 // PS: the update of sample b with coefs[b]; noise and the Philox stream are indexed as step 0 of a
 // shared-t call (extdm_sampler_step), so a sample's result does not depend on which form ran it.
-template <bool PS>
+// HIST (shared t only): the DPM-Solver++(2M) update of the chunk with x0_prev, as in
+// sampler_step_kernel<true>.
+template <bool PS, bool HIST>
 __global__ __launch_bounds__(SNT) void sampler_final_kernel(float* x, const float* eps, int n, const StepCoef* coefs,
                                                             const int* step_ctr, const float* noise, int B,
                                                             uint64_t seed, int sample_base, int round, int k_lo,
-                                                            int k_hi, float q_w, float* thresh_out, unsigned* ws) {
+                                                            int k_hi, float q_w, float* thresh_out, unsigned* ws,
+                                                            float* x0_prev) {
   __shared__ float vs[2];
   const SelLayout L{(int)gridDim.y, (int)gridDim.x};
   const int b = blockIdx.y;
@@ -310,8 +331,38 @@ __global__ __launch_bounds__(SNT) void sampler_final_kernel(float* x, const floa
 #endif
   float* xb = x + (long)b * n;
   const float* eb = eps + (long)b * n;
-  const float* nb = noise ? noise + ((long)step * B + b) * n : nullptr;
   const int e0 = blockIdx.x * SCH, e1 = min(n, e0 + SCH);
+  if (HIST) {
+    float* pb = x0_prev + (long)b * n;
+    // xc: the thresholded x0 (the next step's history); returns the updated x
+    auto update2m = [&](float xv, float ev, float pv, float& xc) __attribute__((always_inline)) {
+      const float x0 = c.sra * xv - c.srm1 * ev;
+      xc = fminf(fmaxf(x0, -s), s) / s;
+      return (c.c2 * xv + c.c1 * xc) + c.c3 * pv;
+    };
+    if ((n & 3) == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(eps) |
+                          reinterpret_cast<uintptr_t>(x0_prev)) & 15) == 0) {
+      for (int e = e0 + 4 * threadIdx.x; e < e1; e += 4 * SNT) {
+        const float4 x4 = *reinterpret_cast<const float4*>(xb + e), e4 = *reinterpret_cast<const float4*>(eb + e);
+        const float4 p4 = *reinterpret_cast<const float4*>(pb + e);
+        float4 o, h;
+        o.x = update2m(x4.x, e4.x, p4.x, h.x);
+        o.y = update2m(x4.y, e4.y, p4.y, h.y);
+        o.z = update2m(x4.z, e4.z, p4.z, h.z);
+        o.w = update2m(x4.w, e4.w, p4.w, h.w);
+        *reinterpret_cast<float4*>(xb + e) = o;
+        *reinterpret_cast<float4*>(pb + e) = h;
+      }
+    } else {
+      for (int e = e0 + threadIdx.x; e < e1; e += SNT) {
+        float xc;
+        xb[e] = update2m(xb[e], eb[e], pb[e], xc);
+        pb[e] = xc;
+      }
+    }
+    return;
+  }
+  const float* nb = noise ? noise + ((long)step * B + b) * n : nullptr;
   auto update = [&](float xv, float ev, float z) __attribute__((always_inline)) {
     const float x0 = c.sra * xv - c.srm1 * ev;
     const float xc = fminf(fmaxf(x0, -s), s) / s;
@@ -587,8 +638,14 @@ __global__ __launch_bounds__(256) void warp_kernel(float* out, const float* src,
 void sampler_step(hipStream_t s, float* x, const float* eps, int B, int n, const StepCoef* coefs,
                   const int* step_ctr, const float* noise, uint64_t seed, int sample_base, int round, int k_lo,
                   int k_hi, float q_w, float* thresh_out) {
-  hipLaunchKernelGGL(sampler_step_kernel, dim3(B), dim3(1024), 0, s, x, eps, n, coefs, step_ctr, noise, B, seed,
-                     sample_base, round, k_lo, k_hi, q_w, thresh_out);
+  hipLaunchKernelGGL(sampler_step_kernel<false>, dim3(B), dim3(1024), 0, s, x, eps, n, coefs, step_ctr, noise, B, seed,
+                     sample_base, round, k_lo, k_hi, q_w, thresh_out, (float*)nullptr);
+}
+
+void sampler_step_hist(hipStream_t s, float* x, const float* eps, float* x0_prev, int B, int n, const StepCoef* coefs,
+                       const int* step_ctr, int k_lo, int k_hi, float q_w, float* thresh_out) {
+  hipLaunchKernelGGL(sampler_step_kernel<true>, dim3(B), dim3(1024), 0, s, x, eps, n, coefs, step_ctr,
+                     (const float*)nullptr, B, (uint64_t)0, 0, 0, k_lo, k_hi, q_w, thresh_out, x0_prev);
 }
 
 size_t sampler_sel_bytes(int B, int n) {
@@ -603,8 +660,21 @@ void sampler_step_mw(hipStream_t s, float* x, const float* eps, int B, int n, co
   hipLaunchKernelGGL((radix_count_kernel<1, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
   hipLaunchKernelGGL((radix_count_kernel<2, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
   hipLaunchKernelGGL((radix_count_kernel<3, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(sampler_final_kernel<false>, grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, noise, B, seed,
-                     sample_base, round, k_lo, k_hi, q_w, thresh_out, ws);
+  hipLaunchKernelGGL((sampler_final_kernel<false, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, noise, B,
+                     seed, sample_base, round, k_lo, k_hi, q_w, thresh_out, ws, (float*)nullptr);
+  if (t_next) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(256), 0, s, step_ctr, coefs, t_next, B, nsteps);
+}
+
+void sampler_step_hist_mw(hipStream_t s, float* x, const float* eps, float* x0_prev, int B, int n,
+                          const StepCoef* coefs, int* step_ctr, int k_lo, int k_hi, float q_w, float* thresh_out,
+                          unsigned* ws, int* t_next, int nsteps) {
+  const dim3 grid((n + SCH - 1) / SCH, B);
+  hipLaunchKernelGGL((radix_count_kernel<0, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<1, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<2, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((radix_count_kernel<3, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr, ws, k_lo, k_hi);
+  hipLaunchKernelGGL((sampler_final_kernel<false, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, step_ctr,
+                     (const float*)nullptr, B, (uint64_t)0, 0, 0, k_lo, k_hi, q_w, thresh_out, ws, x0_prev);
   if (t_next) hipLaunchKernelGGL(sampler_advance_kernel, dim3(1), dim3(256), 0, s, step_ctr, coefs, t_next, B, nsteps);
 }
 
@@ -615,8 +685,8 @@ void sampler_step_t(hipStream_t s, float* x, const float* eps, int B, int n, con
   hipLaunchKernelGGL((radix_count_kernel<1, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
   hipLaunchKernelGGL((radix_count_kernel<2, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
   hipLaunchKernelGGL((radix_count_kernel<3, true>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, ws, k_lo, k_hi);
-  hipLaunchKernelGGL(sampler_final_kernel<true>, grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, noise, B,
-                     (uint64_t)0, 0, 0, k_lo, k_hi, q_w, thresh_out, ws);
+  hipLaunchKernelGGL((sampler_final_kernel<true, false>), grid, dim3(SNT), 0, s, x, eps, n, coefs, nullptr, noise, B,
+                     (uint64_t)0, 0, 0, k_lo, k_hi, q_w, thresh_out, ws, (float*)nullptr);
 }
 
 void q_sample(hipStream_t s, float* xt, const float* x0, const float* noise, float* noise_out, int B, int n,

@@ -23,6 +23,7 @@
  *   extdm_sampler_step   one p_sample / DDIM update given eps
  *                                                   Diffusion.py:145-177, 231-255
  *   extdm_sampler_step_t the same update with a per-sample t (p_sample with a mixed t)
+ *   extdm_sampler_step_hist  one DPM-Solver++(2M) update given eps (no reference counterpart)
  *   extdm_q_sample       GaussianDiffusion.q_sample                 Diffusion.py:276-284
  *   extdm_x0_loss        p_losses after the denoiser (loss, thresholded x0)
  *                                                   Diffusion.py:294-319
@@ -68,7 +69,9 @@ typedef struct ExtdmHandle ExtdmHandle;
  *   WO_REF   DenoiseNet_STWAtt_w_wo_ref_adaptor_cross_multi.py: SMMNIST (tc-1 cond frames,
  *            cond_fea at latent resolution, fea: [B,fea_ch,tc-1+tp,L,L]) */
 enum { EXTDM_ARCH_U12 = 0, EXTDM_ARCH_ADA = 1, EXTDM_ARCH_ADA_U22 = 2, EXTDM_ARCH_WO_REF = 3 };
-enum { EXTDM_SAMPLER_DDPM = 0, EXTDM_SAMPLER_DDIM = 1 };
+/* DPMPP: DPM-Solver++(2M), the data-prediction second-order multistep solver of Lu et al. 2022.
+ * Not part of the reference; deterministic (no noise term). */
+enum { EXTDM_SAMPLER_DDPM = 0, EXTDM_SAMPLER_DDIM = 1, EXTDM_SAMPLER_DPMPP = 2 };
 /* Arithmetic of the direct convolutions (every tensor stays fp32):
  *   FP32   v_mfma_f32_32x32x2_f32 (exact fp32 products and sums)
  *   F16X3  fp32 operands split as hi + lo fp16 pairs, three fp16 MFMAs per product
@@ -126,7 +129,11 @@ int extdm_unet_forward(ExtdmHandle* h, int B, const float* x, const int64_t* t, 
 /* Whole reverse loop. times[k] is the model timestep of step k and
  * times_next[k] the DDIM target (ignored for DDPM). x_T (device, may be NULL:
  * Philox stream), noise (device [S][B][n] or NULL: Philox stream), out (device
- * [B,3,tp,L,L]) receives x_0. use_graph != 0 replays one captured step. */
+ * [B,3,tp,L,L]) receives x_0. use_graph != 0 replays one captured step.
+ * EXTDM_SAMPLER_DPMPP: times must be strictly decreasing; step k goes from times[k] to
+ * times[k + 1] and the last step to the clean sample. eta and times_next are ignored and a
+ * non-NULL noise is an error. The handle's first such call allocates a [max_batch][n] fp32
+ * history buffer (the previous step's thresholded x0), cleared at the start of every call. */
 int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, const int* times_next, float eta,
                  const float* x_cond, const float* cond_fea, const float* x_T, const float* noise, uint64_t seed,
                  int sample_base, int round, float* out, int use_graph, void* stream);
@@ -137,9 +144,24 @@ int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, co
  * p_mean_variance, Diffusion.py:150-163); the step itself is unchanged. */
 int extdm_record_thresholds(ExtdmHandle* h, float* buf, int64_t cap);
 
-/* One sampler update in place on x given eps (the step-k coefficients). */
+/* One sampler update in place on x given eps (the step-k coefficients). DDPM and DDIM only:
+ * EXTDM_SAMPLER_DPMPP is an error here and in extdm_sampler_step_t (extdm_sampler_step_hist). */
 int extdm_sampler_step(ExtdmHandle* h, int B, int sampler, int t, int t_next, float eta, float* x, const float* eps,
                        const float* noise, float* thresh_out, void* stream);
+
+/* One DPM-Solver++(2M) update in place on x given eps, from t towards t_next with t_prev the
+ * step before (t_prev > t > t_next). x0 = the thresholded sqrt_recip[t] x - sqrt_recipm1[t] eps
+ * as in every other sampler; with alpha = sqrt(alphas_cumprod), sigma = sqrt(1 - alphas_cumprod),
+ * lambda = log(alpha / sigma), h = lambda(t_next) - lambda(t), r = (lambda(t) - lambda(t_prev)) / h
+ * and a = alpha(t_next) (1 - exp(-h)), computed in fp64 and rounded once to fp32:
+ *   x = ((sigma(t_next) / sigma(t)) x + a (1 + 1 / (2 r)) x0) + (-a / (2 r)) x0_prev
+ * in fp32 in that order (three products, no contraction), then x0_prev = x0. t_prev < 0: the
+ * first-order start (x0 weight a, history weight 0); t_next < 0: the final step, x = x0.
+ * x0_prev: device [B][n], read and written. x and x0_prev must hold finite values even where
+ * their weight is 0 (first and final step): 0 times a non-finite value is NaN.
+ * thresh_out: [B] or NULL. The step extdm_sample replays for EXTDM_SAMPLER_DPMPP. */
+int extdm_sampler_step_hist(ExtdmHandle* h, int B, int t_prev, int t, int t_next, float* x, const float* eps,
+                            float* x0_prev, float* thresh_out, void* stream);
 
 /* ---- Teacher-forced evaluation step (Diffusion.py:276-327), inference only --------------
  * Every t (and t_next) is a device int64 [B] vector as in extdm_unet_forward, each in
