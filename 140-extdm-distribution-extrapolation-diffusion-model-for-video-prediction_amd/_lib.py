@@ -31,8 +31,9 @@ SAMPLER_DDIM = 1
 SAMPLER_DPMPP = 2  # DPM-Solver++(2M)
 LOSS_TYPES = {'l1': 0, 'l2': 1}  # include/extdm.h EXTDM_LOSS_*
 
-# include/extdm.h EXTDM_PRECISION_*: arithmetic of the direct convolutions
-PRECISIONS = {'fp32': 0, 'f16x3': 1, 'bf16_attn': 2}
+# include/extdm.h EXTDM_PRECISION_*: arithmetic of the direct convolutions ('f16_conv' / 'f16': one
+# fp16 MFMA term per product in the denoiser forward's convs, 'f16' with the bf16 attention too)
+PRECISIONS = {'fp32': 0, 'f16x3': 1, 'bf16_attn': 2, 'f16_conv': 3, 'f16': 4}
 DEFAULT_PRECISION = os.environ.get('EXTDM_PRECISION', 'f16x3')
 
 class ExtdmConfig(ctypes.Structure):

@@ -64,7 +64,10 @@ __device__ __forceinline__ float act_apply(float v, int act) {
 // computed once per group, the channel planes are wave-uniform bases (saddr loads), and the
 // nearest-x2 up convs gather the same way. For the 3x3 / 7x7 / up convs the ci-major order
 // leaves to the per-element path (32 % KH * KW != 0).
-template <int KH, int KW, int BM, int MODE, bool FAST = false, bool TAPK = false>
+// TERMS = 1 (ConvEpi::terms, the F16_CONV / F16 modes): ah bh alone -- the gathered B tile is
+// converted once (hi2c) and only its hi block stored and read; the packed A tile is copied whole
+// (its lo fragments unread), so the LDS layout is the three-term one.
+template <int KH, int KW, int BM, int MODE, bool FAST = false, bool TAPK = false, int TERMS = 3>
 __global__ __launch_bounds__(256) void conv_gemm_x3_kernel(GArgs a) {
   constexpr int WAVES_M = BM >= 64 ? 2 : 1;
   constexpr int WAVES_N = 4 / WAVES_M;
@@ -225,7 +228,8 @@ __global__ __launch_bounds__(256) void conv_gemm_x3_kernel(GArgs a) {
       float am = 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        split2s(breg[g2][2 * e], breg[g2][2 * e + 1], hw[e], lw[e]);
+        if (TERMS == 1) { hw[e] = hi2c(breg[g2][2 * e], breg[g2][2 * e + 1]); lw[e] = 0u; }
+        else split2s(breg[g2][2 * e], breg[g2][2 * e + 1], hw[e], lw[e]);
         amax2(am, breg[g2][2 * e], breg[g2][2 * e + 1]);
       }
       bad |= am >= 65504.f;
@@ -233,7 +237,7 @@ __global__ __launch_bounds__(256) void conv_gemm_x3_kernel(GArgs a) {
       const h8 lo = __builtin_bit_cast(h8, u32x4{lw[0], lw[1], lw[2], lw[3]});
       _Float16* d = Bs + ((g >> 1) * BN + col) * 16 + 8 * ((g & 1) ^ ((col >> 3) & 1));
       *reinterpret_cast<h8*>(d) = hi;
-      *reinterpret_cast<h8*>(d + 2 * BN * 16) = lo;
+      if (TERMS != 1) *reinterpret_cast<h8*>(d + 2 * BN * 16) = lo;
     }
     u32x4* ad = reinterpret_cast<u32x4*>(As);
 #pragma unroll
@@ -264,15 +268,25 @@ __global__ __launch_bounds__(256) void conv_gemm_x3_kernel(GArgs a) {
       for (int i = 0; i < TM; ++i) {
         const _Float16* p = As + ((s * M32 + wm * TM + i) * 2) * 512 + lane * 8;
         ah[i] = *reinterpret_cast<const h8*>(p);
-        al[i] = *reinterpret_cast<const h8*>(p + 512);
-        ad[i] = lo_dn(ah[i]);  // pairs with the scaled B lo (split2s, kernels.h)
+        if (TERMS != 1) {
+          al[i] = *reinterpret_cast<const h8*>(p + 512);
+          ad[i] = lo_dn(ah[i]);  // pairs with the scaled B lo (split2s, kernels.h)
+        }
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
         const int nc = (wn * TN + j) * 32 + lc;
         const _Float16* p = Bs + (s * BN + nc) * 16 + 8 * (h ^ ((nc >> 3) & 1));
         bh[j] = *reinterpret_cast<const h8*>(p);
-        bl[j] = *reinterpret_cast<const h8*>(p + 2 * BN * 16);
+        if (TERMS != 1) bl[j] = *reinterpret_cast<const h8*>(p + 2 * BN * 16);
+      }
+      if (TERMS == 1) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int j = 0; j < TN; ++j)
+            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+        continue;
       }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -325,17 +339,23 @@ __global__ __launch_bounds__(256) void conv_gemm_x3_kernel(GArgs a) {
   }
 }
 
-template <int KH, int KW, int BM, int MODE, bool FAST, bool TAPK = false>
+template <int KH, int KW, int BM, int MODE, bool FAST, bool TAPK = false, int TERMS = 3>
 void launch_f(hipStream_t s, const GArgs& a, dim3 grid) {
+  if constexpr (TERMS == 3) {
+    if (a.e.terms == 1) {
+      launch_f<KH, KW, BM, MODE, FAST, TAPK, 1>(s, a, grid);
+      return;
+    }
+  }
   constexpr int AH = 2 * (BM / 32) * 2 * 512, BH = 2 * 2 * BN * 16;
   const size_t lds = (size_t)2 * (AH + BH) * sizeof(_Float16);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_x3_kernel<KH, KW, BM, MODE, FAST, TAPK>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gemm_x3_kernel<KH, KW, BM, MODE, FAST, TAPK, TERMS>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL((conv_gemm_x3_kernel<KH, KW, BM, MODE, FAST, TAPK>), grid, dim3(256), lds, s, a);
+  hipLaunchKernelGGL((conv_gemm_x3_kernel<KH, KW, BM, MODE, FAST, TAPK, TERMS>), grid, dim3(256), lds, s, a);
 }
 
 // the tap-major gather (TAPK above): a tap-major packing, whole 8-channel groups per source,

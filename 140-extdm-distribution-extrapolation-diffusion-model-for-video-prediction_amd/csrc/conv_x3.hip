@@ -196,7 +196,8 @@ template <> struct XMaxX3<5, 256> { static constexpr int v = 400; };
 // pixel, table [P][H W] (channel LayerNorm ahead of a 1x1 conv, gamma folded into the weight: m =
 // mean, r = 1 / sqrt(var + eps)): one pair per staging slot, loaded once in the prologue.
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF, bool SPAN, int NS, bool XOP = false,
-          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false, int TT = 0, int AFF = 0>
+          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, bool BX = false, int TT = 0, int AFF = 0,
+          int TERMS = 3>
 __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4 && KS == 5 ? 2 : 1))) void conv_x3_kernel(X3Args a) {
   constexpr int NT = NW * 64;
   constexpr int PAD = KS / 2;
@@ -209,6 +210,7 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
   constexpr int STG = KT / KY;                  // stages per channel block
   static_assert(KT % KY == 0, "KY must divide the taps");
   static_assert(!TT || (KS == 3 && NG == 1 && BX && SPAN && !XOP && !WS && !PH && SPL == 0), "TT: staged 3x3 geometry");
+  static_assert(TERMS == 3 || (TERMS == 1 && SPAN && !WS && SPL != 2), "TERMS = 1: the spanning-barrier tiles, no WS");
   constexpr int NSLOT = NS;
   constexpr int WM = NW / WN;
   constexpr int TM = BM / (32 * WM);
@@ -453,11 +455,14 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
 #pragma unroll
         for (int c = 0; c < 16; ++c) v[c] = (v[c] - amr[j].x) * amr[j].y;
       }
+      // TERMS = 1: the hi halves alone (one conversion per pair, hi2c), the lo blocks of the slot
+      // are neither written nor read; the range check is the same
       unsigned hw[8], lw[8];
       float am = 0.f;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
-        split2s(v[2 * c], v[2 * c + 1], hw[c], lw[c]);
+        if (TERMS == 1) { hw[c] = hi2c(v[2 * c], v[2 * c + 1]); lw[c] = 0u; }
+        else split2s(v[2 * c], v[2 * c + 1], hw[c], lw[c]);
         amax2(am, v[2 * c], v[2 * c + 1]);
       }
       range_bad |= am >= 65504.f;
@@ -470,8 +475,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
         _Float16* d = Xs + (used ? spos[j] : XPL / 8 - 1) * 8;
         *reinterpret_cast<h8*>(d) = hi0;
         *reinterpret_cast<h8*>(d + XPL) = hi1;
-        *reinterpret_cast<h8*>(d + 2 * XPL) = lo0;
-        *reinterpret_cast<h8*>(d + 3 * XPL) = lo1;
+        if (TERMS != 1) {
+          *reinterpret_cast<h8*>(d + 2 * XPL) = lo0;
+          *reinterpret_cast<h8*>(d + 3 * XPL) = lo1;
+        }
         continue;
       }
       const int sw = (spos[j] >> 3) & 1;
@@ -479,8 +486,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       _Float16* dl = used ? dh + XLO : xdummy + 16;
       *reinterpret_cast<h8*>(dh + 8 * sw) = hi0;
       *reinterpret_cast<h8*>(dh + 8 * (sw ^ 1)) = hi1;
-      *reinterpret_cast<h8*>(dl + 8 * sw) = lo0;
-      *reinterpret_cast<h8*>(dl + 8 * (sw ^ 1)) = lo1;
+      if (TERMS != 1) {
+        *reinterpret_cast<h8*>(dl + 8 * sw) = lo0;
+        *reinterpret_cast<h8*>(dl + 8 * (sw ^ 1)) = lo1;
+      }
     }
   };
   constexpr int NPIECE = AHS / 512;  // 1 KiB pieces
@@ -504,7 +513,8 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
     const _Float16* src = a.xop + (long)cgb * a.xop_cg + (long)tb * 8;
     const int npc = (a.XPOS + 63) >> 6;  // 1 KiB pieces per plane
     if (WS && wave_u < NW / 2) return;  // WS: the X waves only
-    for (int pc = WS ? wave_u - NW / 2 : wave_u; pc < 4 * npc; pc += (WS ? NW / 2 : NW)) {
+    // TERMS = 1: the two hi planes (pl = 0, 1) only
+    for (int pc = WS ? wave_u - NW / 2 : wave_u; pc < (TERMS == 1 ? 2 : 4) * npc; pc += (WS ? NW / 2 : NW)) {
       const int pl = pc / npc, k = pc - pl * npc;  // pl = 2 * hl + c8
       glds16_asm(src + (pl >> 1) * a.xop_hl + (pl & 1) * (a.xop_hl >> 1) + k * 512 + lane * 8,
                  Xs + pl * XPL + k * 512);
@@ -659,20 +669,26 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
       const int ix = line == 2 ? 0 : (line == 3 ? a.W - 1 : jj);
       if (q >= a.P || iy < row0 || iy >= row0 + a.TH) continue;
       const int pos = (pp * THK + iy - row0 + PAD) * a.RS + ix + PAD;
-      h8 h0, h1, l0, l1;
+      // TERMS = 1: the staged hi alone (the lo blocks are not written): the edge kernels then see
+      // the operand this conv multiplies, as in the three-term case
+      h8 h0, h1, l0 = {}, l1 = {};
       if (LIN) {
         const _Float16* xh = Xs + (long)pos * 8;
         h0 = *reinterpret_cast<const h8*>(xh);
         h1 = *reinterpret_cast<const h8*>(xh + XPL);
-        l0 = *reinterpret_cast<const h8*>(xh + 2 * XPL);
-        l1 = *reinterpret_cast<const h8*>(xh + 3 * XPL);
+        if (TERMS != 1) {
+          l0 = *reinterpret_cast<const h8*>(xh + 2 * XPL);
+          l1 = *reinterpret_cast<const h8*>(xh + 3 * XPL);
+        }
       } else {
         const int sw = (pos >> 3) & 1;
         const _Float16* xh = Xs + (long)pos * 16;
         h0 = *reinterpret_cast<const h8*>(xh + 8 * sw);
         h1 = *reinterpret_cast<const h8*>(xh + 8 * (sw ^ 1));
-        l0 = *reinterpret_cast<const h8*>(xh + XLO + 8 * sw);
-        l1 = *reinterpret_cast<const h8*>(xh + XLO + 8 * (sw ^ 1));
+        if (TERMS != 1) {
+          l0 = *reinterpret_cast<const h8*>(xh + XLO + 8 * sw);
+          l1 = *reinterpret_cast<const h8*>(xh + XLO + 8 * (sw ^ 1));
+        }
       }
       float v[16];
 #pragma unroll
@@ -718,8 +734,10 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
         for (int i = 0; i < TM; ++i) {
           const _Float16* ap = As + ((step * MT32 + wm * TM + i) * 2) * 512 + lane * 8;
           ah[i] = *reinterpret_cast<const h8*>(ap);
-          al[i] = *reinterpret_cast<const h8*>(ap + 512);
-          ad[i] = lo_dn(ah[i]);  // pairs with the scaled activation lo (split2s, kernels.h)
+          if (TERMS != 1) {
+            al[i] = *reinterpret_cast<const h8*>(ap + 512);
+            ad[i] = lo_dn(ah[i]);  // pairs with the scaled activation lo (split2s, kernels.h)
+          }
         }
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
@@ -727,7 +745,15 @@ __global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu(NW == 4
           const _Float16* bp = (XOP || LIN) ? Xs + h * XPL + pos * 8
                                             : Xs + ((long)g * a.XPOS + pos) * 16 + 8 * (h ^ ((pos >> 3) & 1));
           bh[j] = *reinterpret_cast<const h8*>(bp);
-          bl[j] = *reinterpret_cast<const h8*>(bp + XLO);
+          if (TERMS != 1) bl[j] = *reinterpret_cast<const h8*>(bp + XLO);
+        }
+        if (TERMS == 1) {  // one term: hi(a) hi(b) into the fp32 accumulator, no lo operand read
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh[j], acc[i][j], 0, 0, 0);
+          continue;
         }
 #pragma unroll
         for (int i = 0; i < TM; ++i)
@@ -964,9 +990,26 @@ bool x3_bufx_ok(const X3Args& a, int cib) {
   return !off && EXTDM_X3_BUFX && a.C0 % 16 == 0 && a.Cin % cib == 0 && a.in0_bytes > 0;
 }
 
+// The tiles with a one-term instantiation (kernel parameter TERMS = 1; ConvEpi::terms): the ones the
+// default routes of the shipped configs launch -- spanning barriers, one ky row per stage, no wave
+// specialisation; the split-K sum (SPL = 2) multiplies nothing and is shared. The tiles only an A/B
+// switch selects (EXTDM_X3_NOSPAN, _V3, _WS, _NW7, _BN7, _BN3, EXTDM_FEA_BM / _TILE) keep their three
+// terms in every mode.
+template <int KS, int KY, int BM, int BN, bool SPAN, int SPL, bool WS, int NW>
+constexpr bool x3_has_one_term() {
+  return SPAN && KY == 1 && !WS && SPL != 2 && !(KS == 7 && (NW == 16 || BN == 256)) && !(KS == 3 && BN == 512) &&
+         !(KS == 5 && BM == 64);
+}
+
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF, bool SPAN, int NS, bool XOP = false,
-          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false>
+          bool RGN = false, int SPL = 0, bool PH = false, bool WS = false, int TERMS = 3>
 void launch_sp(hipStream_t s, const X3Args& a, unsigned ntiles) {
+  if constexpr (TERMS == 3 && x3_has_one_term<KS, KY, BM, BN, SPAN, SPL, WS, NW>()) {
+    if (a.e.terms == 1) {
+      launch_sp<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS, 1>(s, a, ntiles);
+      return;
+    }
+  }
   constexpr int AH = KY * NG * KS * (BM / 32) * 2 * 512;
   constexpr bool WSR = WS && !XOP;
   constexpr bool LIN = WSR || ((EXTDM_X3_LIN == 1 || (EXTDM_X3_LIN == 2 && KS >= 5)) && NG == 1 && !XOP);
@@ -980,24 +1023,23 @@ void launch_sp(hipStream_t s, const X3Args& a, unsigned ntiles) {
   // BX only where the staging loads run (not the operand-input / WS-raw / split-K-sum tiles)
   constexpr bool BXV = !XOP && !WSR && SPL != 2 && SPAN;
   const bool bx = BXV && x3_bufx_ok(a, 16 * NG);
+  const auto kern = &conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS, false, 0, 0, TERMS>;
+  const auto kern_bx = &conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS, BXV, 0, 0, TERMS>;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     if (BXV)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS, BXV>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern_bx), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
   if (SPL != 2) {
     auto tf = [](bool v) { return v ? "true" : "false"; };
-    note_kernel("conv_x3_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %s, %d, %s, %s, %s>", KS, KY, BM, BN, NG, WN,
-                NW, XBUF, tf(SPAN), NS, tf(XOP), tf(RGN), SPL, tf(PH), tf(WS), tf(bx));
+    // the three-term name is the one it always was; a one-term launch spells out TT, AFF and TERMS
+    note_kernel("conv_x3_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %s, %d, %s, %s, %d, %s, %s, %s%s>", KS, KY, BM, BN, NG, WN,
+                NW, XBUF, tf(SPAN), NS, tf(XOP), tf(RGN), SPL, tf(PH), tf(WS), tf(bx), TERMS == 1 ? ", 0, 0, 1" : "");
   }
-  if (bx)
-    hipLaunchKernelGGL((conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS, BXV>), grid, dim3(NW * 64), lds, s, a);
-  else
-    hipLaunchKernelGGL((conv_x3_kernel<KS, KY, BM, BN, NG, WN, NW, XBUF, SPAN, NS, XOP, RGN, SPL, PH, WS>), grid, dim3(NW * 64), lds, s, a);
+  if (bx) hipLaunchKernelGGL(kern_bx, grid, dim3(NW * 64), lds, s, a);
+  else hipLaunchKernelGGL(kern, grid, dim3(NW * 64), lds, s, a);
 }
 
 template <int KS, int KY, int BM, int BN, int NG, int WN, int NW, int XBUF, bool SPAN>
@@ -1271,16 +1313,22 @@ bool x3_bn256(const View& out, const PackedW& w, const ConvEpi& epi) {
 namespace {
 
 // One launch with the input affine (kernel note AFF): KY = 1, two X buffers, spanning barriers, BX staging
-template <int KS, int BM, int BN, int NG, int WN, int NW, int NS, int SPL, int AFF>
+template <int KS, int BM, int BN, int NG, int WN, int NW, int NS, int SPL, int AFF, int TERMS = 3>
 void launch_aff(hipStream_t s, const X3Args& a, unsigned ntiles, size_t lds) {
-  const auto kern = &conv_x3_kernel<KS, 1, BM, BN, NG, WN, NW, 2, true, NS, false, false, SPL, false, false, true, 0, AFF>;
+  if constexpr (TERMS == 3 && SPL != 2) {
+    if (a.e.terms == 1) {
+      launch_aff<KS, BM, BN, NG, WN, NW, NS, SPL, AFF, 1>(s, a, ntiles, lds);
+      return;
+    }
+  }
+  const auto kern = &conv_x3_kernel<KS, 1, BM, BN, NG, WN, NW, 2, true, NS, false, false, SPL, false, false, true, 0, AFF, TERMS>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  note_kernel("conv_x3_kernel<%d, 1, %d, %d, %d, %d, %d, 2, true, %d, false, false, %d, false, false, true, 0, %d>", KS, BM,
-              BN, NG, WN, NW, NS, SPL, AFF);
+  note_kernel("conv_x3_kernel<%d, 1, %d, %d, %d, %d, %d, 2, true, %d, false, false, %d, false, false, true, 0, %d%s>", KS, BM,
+              BN, NG, WN, NW, NS, SPL, AFF, TERMS == 1 ? ", 1" : "");
   hipLaunchKernelGGL(kern, dim3(ntiles, (a.Cout + BM - 1) / BM, SPL == 1 ? a.nsplit : 1), dim3(NW * 64), lds, s, a);
 }
 
@@ -1627,19 +1675,25 @@ bool conv_x3_forward_op(hipStream_t s, const View& out, const X3Op& in, const Pa
 namespace {
 
 // One two-tap launch (kernel note TT): the staged 3x3 tiles of x3_tile(3, Cout) with BX staging
-template <int TT, int BM, int BN, int WN, int NW, int NS>
+template <int TT, int BM, int BN, int WN, int NW, int NS, int TERMS = 3>
 void launch_tt(hipStream_t s, const X3Args& a, unsigned ntiles, unsigned mtiles) {
+  if constexpr (TERMS == 3) {
+    if (a.e.terms == 1) {
+      launch_tt<TT, BM, BN, WN, NW, NS, 1>(s, a, ntiles, mtiles);
+      return;
+    }
+  }
   constexpr int AH = 2 * (BM / 32) * 2 * 512;  // halves per ky' slice: two kx' steps
   const size_t xlo = (size_t)a.XPOS * 16;
   const size_t lds = ((size_t)2 * AH + 2 * 2 * xlo + 32 + 4 * BM) * sizeof(_Float16);
-  const auto kern = &conv_x3_kernel<3, 1, BM, BN, 1, WN, NW, 2, true, NS, false, false, 0, false, false, true, TT>;
+  const auto kern = &conv_x3_kernel<3, 1, BM, BN, 1, WN, NW, 2, true, NS, false, false, 0, false, false, true, TT, 0, TERMS>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  note_kernel("conv_x3_kernel<3, 1, %d, %d, 1, %d, %d, 2, true, %d, false, false, 0, false, false, true, %d>", BM, BN, WN,
-              NW, NS, TT);
+  note_kernel("conv_x3_kernel<3, 1, %d, %d, 1, %d, %d, 2, true, %d, false, false, 0, false, false, true, %d%s>", BM, BN, WN,
+              NW, NS, TT, TERMS == 1 ? ", 0, 1" : "");
   hipLaunchKernelGGL(kern, dim3(ntiles, mtiles), dim3(NW * 64), lds, s, a);
 }
 

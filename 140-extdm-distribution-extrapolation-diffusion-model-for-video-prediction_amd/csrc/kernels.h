@@ -101,6 +101,13 @@ __device__ __forceinline__ void split2m(float a, float b, f16x2_t& hi, f16x2_t& 
 __device__ __forceinline__ void amax2(float& m, float a, float b) {
   asm("v_max3_f32 %0, |%1|, |%2|, %0" : "+v"(m) : "v"(a), "v"(b));
 }
+// One-term operand of the F16_CONV / F16 modes (ConvEpi::terms == 1): hi = fp16_rn(v) of a pair,
+// packed, and nothing else -- the product is hi(a) hi(b) alone. Compiler-visible (one
+// v_cvt_pk_f16_f32), so hipcc places the MFMA hazard waits itself. A value with |v| >= 65520
+// converts to inf: the staging still raises the range flag at |v| >= 65504 (amax2).
+__device__ __forceinline__ unsigned hi2c(float a, float b) {
+  return __builtin_bit_cast(unsigned, __builtin_convertvector((f32x2_t){a, b}, f16x2_t));
+}
 
 // The template of the last attention launch on this thread (extdm_bench_layer_kernel: bench.py
 // prices a layer by the arithmetic of the kernel it actually launched). printf-style.
@@ -197,6 +204,10 @@ struct ConvEpi {
   int in_aff_mode = 0;
   const float2* in_aff = nullptr;
   int post_first = 0;
+  // fp16 MFMA terms per product of the conv_x3 / conv_gemm_x3 / pw_x3 kernels: 3 = f16x3 (al bh +
+  // ah bh + ah' bl'), 1 = ah bh alone (EXTDM_PRECISION_F16_CONV / _F16, set per launch by the handle
+  // while a denoiser forward runs; a kernel without a one-term variant runs its three terms)
+  int terms = 3;
 };
 
 // Input channels per half-stage of the halo conv for kernel size ks and tile bm.

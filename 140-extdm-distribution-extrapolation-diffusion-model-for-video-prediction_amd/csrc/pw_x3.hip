@@ -80,6 +80,9 @@ __device__ __forceinline__ void pw_dma(__amdgpu_buffer_rsrc_t rs, int voff, int 
                : "memory");
 }
 
+// TERMS = 1 (ConvEpi::terms, the F16_CONV / F16 modes): ah bh alone -- no weight lo fragments in
+// registers, no lo half staged or read (the slot layout is unchanged, its lo half unused).
+template <int TERMS = 3>
 __global__ __launch_bounds__(512) void pw_x3_kernel(PwArgs a) {
   extern __shared__ __attribute__((aligned(16))) _Float16 sm[];
   float* const esb = reinterpret_cast<float*>(sm + PW_NKC * PW_SLOT);  // [scale 256][bias 256]
@@ -92,13 +95,16 @@ __global__ __launch_bounds__(512) void pw_x3_kernel(PwArgs a) {
   for (int s = 0; s < PW_KS; ++s) {
     const _Float16* wp = a.w + ((long)(s * 8 + wave) * 2) * 512 + lane * 8;
     ah[s] = *reinterpret_cast<const h8*>(wp);
-    al[s] = *reinterpret_cast<const h8*>(wp + 512);
+    if (TERMS != 1) al[s] = *reinterpret_cast<const h8*>(wp + 512);
   }
   // retired here, before any chunk load: a weight load still pending in hipcc's count at its
   // first MFMA use inside the tile loop put a static vmcnt wait there that, with the chunk
   // loads outside that count, drained the prefetch on every pass
 #pragma unroll
-  for (int s = 0; s < PW_KS; ++s) asm volatile("" ::"v"(ah[s]), "v"(al[s]));
+  for (int s = 0; s < PW_KS; ++s) {
+    if (TERMS != 1) asm volatile("" ::"v"(ah[s]), "v"(al[s]));
+    else asm volatile("" ::"v"(ah[s]));
+  }
   if (tid < PW_M) {
     esb[tid] = a.wscale[tid];
     esb[PW_M + tid] = a.bias ? a.bias[tid] : 0.f;
@@ -166,12 +172,13 @@ __global__ __launch_bounds__(512) void pw_x3_kernel(PwArgs a) {
     unsigned hw[4], lw[4];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      split2s(x[2 * c], x[2 * c + 1], hw[c], lw[c]);
+      if (TERMS == 1) { hw[c] = hi2c(x[2 * c], x[2 * c + 1]); lw[c] = 0u; }
+      else split2s(x[2 * c], x[2 * c + 1], hw[c], lw[c]);
       amax2(am, x[2 * c], x[2 * c + 1]);
     }
     _Float16* d = sm + slot * PW_SLOT + (wave * PW_NPX + lane) * 8;
     *reinterpret_cast<h8*>(d) = __builtin_bit_cast(h8, u32x4{hw[0], hw[1], hw[2], hw[3]});
-    *reinterpret_cast<h8*>(d + PW_SLOT / 2) = __builtin_bit_cast(h8, u32x4{lw[0], lw[1], lw[2], lw[3]});
+    if (TERMS != 1) *reinterpret_cast<h8*>(d + PW_SLOT / 2) = __builtin_bit_cast(h8, u32x4{lw[0], lw[1], lw[2], lw[3]});
   };
 
   f32x16 acc[2];
@@ -217,7 +224,12 @@ __global__ __launch_bounds__(512) void pw_x3_kernel(PwArgs a) {
         for (int j = 0; j < 2; ++j) {
           const _Float16* bp = sl + ((2 * ks + h) * PW_NPX + 32 * j + lc) * 8;
           bh[j] = *reinterpret_cast<const h8*>(bp);
-          bl[j] = *reinterpret_cast<const h8*>(bp + PW_SLOT / 2);
+          if (TERMS != 1) bl[j] = *reinterpret_cast<const h8*>(bp + PW_SLOT / 2);
+        }
+        if (TERMS == 1) {
+#pragma unroll
+          for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[s], bh[j], acc[j], 0, 0, 0);
+          continue;
         }
         // opaque per tile: hoisted out of the tile loop, the 16 lo_dn products would take 64 more
         // VGPRs than the register file has left (scratch spills)
@@ -314,11 +326,14 @@ bool pw_x3_forward(hipStream_t s, const View& out, const View& in, const PackedW
   const size_t lds = (size_t)PW_NKC * PW_SLOT * 2 + 2 * PW_M * 4 + (EXTDM_PW_MANUAL ? (size_t)PW_NKC * PW_KC * PW_NPX * 4 : 0);
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_x3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_x3_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              160 * 1024);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pw_x3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               160 * 1024);
     attr = true;
   }
-  hipLaunchKernelGGL(pw_x3_kernel, dim3(grid), dim3(512), lds, s, a);
+  if (e.terms == 1) hipLaunchKernelGGL(pw_x3_kernel<1>, dim3(grid), dim3(512), lds, s, a);
+  else hipLaunchKernelGGL(pw_x3_kernel<3>, dim3(grid), dim3(512), lds, s, a);
   return true;
 }
 

@@ -320,6 +320,7 @@ struct ExtdmHandle {
       const View rp = cf_view(fake, Bm, cfg.dim, T, L, L).frames(tm(), cfg.tp);
       const View f = cf_view(fake, Bm, cfg.fea_ch, cfg.tp, fs, fs);
       ConvEpi e;
+      e.terms = conv_terms;
       e.res = rp.p; e.res_sb = rp.sb; e.res_sc = rp.sc; e.res_st = rp.st;
       ok = conv_x3_phase_forward(nullptr, rp, f, w5, e, fake, true) &&
            fea_edges_forward(nullptr, rp, fake, cfg.fea_ch, fw.side, fw.side_scale, fw.corner, true);
@@ -345,6 +346,7 @@ struct ExtdmHandle {
     float* edge = arena.alloc(fea_edge_floats(f.B * f.T, f.C, f.H));
     if (plan) return;
     ConvEpi e;
+    e.terms = conv_terms;
     e.res = rp.p; e.res_sb = rp.sb; e.res_sc = rp.sc; e.res_st = rp.st;
     REQUIRE(conv_x3_phase_forward(s, rp, f, w5, e, edge), "phase-composed init_conv launch rejected");
     REQUIRE(fea_edges_forward(s, rp, edge, f.C, fw.side, fw.side_scale, fw.corner), "init_conv edge corrections rejected");
@@ -408,6 +410,7 @@ struct ExtdmHandle {
     }
     if (plan) return 0;
     ConvEpi e;
+    e.terms = conv_terms;
     e.bias = bias;
     e.stats = stats;
     e.stats_groups = stats_groups;
@@ -449,6 +452,7 @@ struct ExtdmHandle {
       float* sw2 = sb2 ? arena.alloc(sb2 / sizeof(float)) : nullptr;
       if (!plan) {
         ConvEpi e;
+        e.terms = conv_terms;
         e.bias = D(p + ".block2.proj.bias");
         e.stats = st;
         e.stats_groups = 8;
@@ -468,6 +472,7 @@ struct ExtdmHandle {
       // block2's GroupNorm + SiLU applied to the residual inside res_conv's epilogue
       if (plan) return;
       ConvEpi e;
+      e.terms = conv_terms;
       e.bias = D(p + ".res_conv.bias");
       e.res = h2.p; e.res_sb = h2.sb; e.res_sc = h2.sc; e.res_st = h2.st;
       e.res_aff = groupnorm_affine(s, h2, 8, D(p + ".block2.norm.weight"), D(p + ".block2.norm.bias"), partials, sp2);
@@ -662,15 +667,28 @@ struct ExtdmHandle {
     const AttnX3Pack a = pack_attn_x3(tq.f, tp.f, tg.f, nb.empty() ? nullptr : &H(nb).f, C, hid, uh, q_scale());
     return attn_x3w[nqkv] = {upload(a.a), upload(std::vector<float>(a.sc, a.sc + 5)), a.s2};
   }
-  // f16x3 convolutions (F16X3, and BF16_ATTN, whose attention core alone is bf16)
-  bool x3_convs() const { return cfg.precision == EXTDM_PRECISION_F16X3 || cfg.precision == EXTDM_PRECISION_BF16_ATTN; }
-  bool bf16_attn() const { return cfg.precision == EXTDM_PRECISION_BF16_ATTN; }
+  // f16x3 convolutions (F16X3, and BF16_ATTN, whose attention core alone is bf16; F16_CONV and F16 are
+  // those two with one MFMA term per product in the denoiser forward's convs: one_term())
+  bool x3_convs() const { return cfg.precision >= EXTDM_PRECISION_F16X3 && cfg.precision <= EXTDM_PRECISION_F16; }
+  bool bf16_attn() const { return cfg.precision == EXTDM_PRECISION_BF16_ATTN || cfg.precision == EXTDM_PRECISION_F16; }
+  // the attention routing of F16X3 (every mode whose attention is not bf16)
+  bool f16x3_attn() const { return x3_convs() && !bf16_attn(); }
+  bool one_term() const { return cfg.precision == EXTDM_PRECISION_F16_CONV || cfg.precision == EXTDM_PRECISION_F16; }
+  // ConvEpi::terms of every conv launched now: 3 outside a denoiser forward (the LFAE entry points,
+  // extdm_decode), 1 inside one on a one_term() handle (ForwardTerms below). Per handle and per
+  // launch: nothing is shared between handles.
+  int conv_terms = 3;
+  struct ForwardTerms {
+    ExtdmHandle* h;
+    explicit ForwardTerms(ExtdmHandle* hh) : h(hh) { h->conv_terms = h->one_term() ? 1 : 3; }
+    ~ForwardTerms() { h->conv_terms = 3; }
+  };
   bool x3_attn_ok(int C, int ntok, int mode) const {
     // read per call: EXTDM_NO_X3_ATTN / _STW / _TEMPORAL route a layer back to the fp32 kernels
     const bool off = env_flag("EXTDM_NO_X3_ATTN"), off_stw = env_flag("EXTDM_NO_X3_STW"), off_tmp = env_flag("EXTDM_NO_X3_TEMPORAL");
     if (off || (mode == 0 && off_stw) || (mode == 1 && off_tmp)) return false;
     // BF16_ATTN: the same fused kernels with the bf16 attention core (dim_head 32)
-    return (cfg.precision == EXTDM_PRECISION_F16X3 || (bf16_attn() && cfg.dim_head == 32)) &&
+    return (f16x3_attn() || (bf16_attn() && cfg.dim_head == 32)) &&
            attn_x3_supported(C, ntok, cfg.dim_head, cfg.heads);
   }
   // the fused 64-token-window route (stw64_x3.hip) in F16X3 and BF16_ATTN; EXTDM_NO_STW64=1 sends
@@ -691,7 +709,7 @@ struct ExtdmHandle {
     if (!(cfg.dim_head == 32 || (cfg.dim_head == 16 && window && !bf16_attn())) || ntok > max_tok) return false;
     if (bf16_attn()) return !fused_x3;
     static const bool off = env_flag("EXTDM_NO_X3_CORE");
-    return cfg.precision == EXTDM_PRECISION_F16X3 && !fused_x3 && !off;
+    return f16x3_attn() && !fused_x3 && !off;
   }
   float q_scale() const { return 1.0f / std::sqrt((float)cfg.dim_head); }
   // model frame count: wo_ref drops the last cond frame (wo_ref.py:911)
@@ -789,7 +807,7 @@ struct ExtdmHandle {
     const int T = x.T;
     REQUIRE(T <= 64 && tb_stride == 64, "temporal attention over more than 64 frames");
     g.per = 64;
-    const bool x3 = cfg.precision == EXTDM_PRECISION_F16X3 || (bf16_attn() && cfg.dim_head == 32);
+    const bool x3 = f16x3_attn() || (bf16_attn() && cfg.dim_head == 32);
     if (x3 && !env_flag("EXTDM_NO_T64") && !env_flag("EXTDM_NO_X3_ATTN") && !env_flag("EXTDM_NO_X3_TEMPORAL") &&
         temporal64_x3_supported(x.C, T, cfg.dim_head, cfg.heads) && out.sb == x.sb && out.sc == x.sc && out.st == x.st &&
         x.st == (long)x.H * x.W && ((long)(x.C - 1) * x.sc + (long)T * x.st) * 4 < (1L << 30)) {  // 31-bit buffer offsets per sample
@@ -803,7 +821,7 @@ struct ExtdmHandle {
       return;
     }
     static const bool off = env_flag("EXTDM_NO_X3_CORE");
-    const bool core = bf16_attn() ? cfg.dim_head == 32 : (cfg.precision == EXTDM_PRECISION_F16X3 && !off);
+    const bool core = bf16_attn() ? cfg.dim_head == 32 : (f16x3_attn() && !off);
     last_core = core;
     Scope sc(arena);
     const int hid = cfg.heads * cfg.dim_head;
@@ -944,6 +962,7 @@ struct ExtdmHandle {
     if (norm) channel_ln_stats(s, st, in0, in1);
     if (!run) return;
     ConvEpi e;
+    e.terms = conv_terms;
     e.bias = bias;
     if (res) { e.res = res->p; e.res_sb = res->sb; e.res_sc = res->sc; e.res_st = res->st; }
     e.split_ws = ws;
@@ -1001,6 +1020,7 @@ struct ExtdmHandle {
         if (!all && !(adaptor_only == 1 && l == ag.L - 1)) continue;
         const View cur = E.frames(0, nl);
         ConvEpi e;
+        e.terms = conv_terms;
         e.res = cur.p; e.res_sb = cur.sb; e.res_sc = cur.sc; e.res_st = cur.st;
         e.post_scale = sd;
         e.post_first = 1;
@@ -2054,6 +2074,8 @@ int extdm_create(const ExtdmConfig* cfg, ExtdmHandle** out) {
     REQUIRE(cfg && out, "null argument");
     REQUIRE(cfg->arch >= EXTDM_ARCH_U12 && cfg->arch <= EXTDM_ARCH_WO_REF, "unsupported Unet3D architecture id");
     REQUIRE(cfg->n_levels >= 1 && cfg->n_levels <= 4, "n_levels must be 1..4");
+    REQUIRE(cfg->precision >= EXTDM_PRECISION_FP32 && cfg->precision <= EXTDM_PRECISION_F16,
+            "precision must be one of EXTDM_PRECISION_*");
     int ndev = 0;
     HIPCHK(hipGetDeviceCount(&ndev));
     REQUIRE(ndev > 0, "no HIP device visible");
@@ -2111,6 +2133,7 @@ int extdm_unet_forward(ExtdmHandle* h, int B, const float* x, const int64_t* t, 
     h->s = reinterpret_cast<hipStream_t>(stream);
     h->bench_stage = 0;
     t_to_int(h->s, t, h->t_batch, B);
+    ExtdmHandle::ForwardTerms terms(h);
     h->unet_forward(B, x, cond, fea, out);
     HIPCHK(hipGetLastError());
   });
@@ -2244,7 +2267,10 @@ int extdm_p_losses(ExtdmHandle* h, int B, const int64_t* t, const float* x_cond,
     q_sample(s, h->xt_buf, x_start, noise, noise ? nullptr : h->noise_buf, B, n, h->qs_coefs, seed, sample_base, round);
     if (h->x3_convs()) x3_range_reset(s);
     t_to_int(s, t, h->t_batch, B);
-    h->unet_forward(B, h->xt_buf, x_cond, cond_fea, h->eps_buf);
+    {
+      ExtdmHandle::ForwardTerms terms(h);
+      h->unet_forward(B, h->xt_buf, x_cond, cond_fea, h->eps_buf);
+    }
     int klo, khi;
     float w;
     h->quantile_ranks(n, klo, khi, w);
@@ -2301,6 +2327,7 @@ int extdm_sample(ExtdmHandle* h, int B, int sampler, int S, const int* times, co
     else fill_normal(s, out, B, n, seed, sample_base, round, 0x7FFFFFFF);
     HIPCHK(hipMemsetAsync(h->step_ctr, 0, sizeof(int), s));
     if (h->x3_convs()) x3_range_reset(s);
+    ExtdmHandle::ForwardTerms terms(h);  // the cond-frame work and every step, captured or eager
     h->prepare_cond(B, x_cond, cond_fea);  // t-independent cond-frame work, once per call
     int klo, khi;
     float w;
@@ -2408,6 +2435,7 @@ int extdm_bench_layer(ExtdmHandle* h, int B, int layer, int iters, float* ms_out
     h->s = s;
     Scope sc(h->arena);
     NoteScope notes;
+    ExtdmHandle::ForwardTerms terms(h);  // the instantiations the forward launches in this mode
     // bench_stage makes stw() / temporal() skip launches: back to 0 however this call ends
     struct StageReset {
       ExtdmHandle* h;
@@ -2546,6 +2574,7 @@ int extdm_bench_layer(ExtdmHandle* h, int B, int layer, int iters, float* ms_out
       const auto& fw = h->Pfea_phase();
       const PackedW& w5 = h->P("init_conv.weight#fea5");
       ConvEpi e;
+      e.terms = h->conv_terms;
       e.res = r.p; e.res_sb = r.sb; e.res_sc = r.sc; e.res_st = r.st;
       const double pl = (double)B * T;
       const double flop = layer == 0 ? pl * fs * fs * 2.0 * 4 * Co * Cf * 25
@@ -2728,6 +2757,7 @@ int extdm_bench_layer(ExtdmHandle* h, int B, int layer, int iters, float* ms_out
     auto launch = [&] {
       if (layer == 5) {
         ConvEpi e;
+        e.terms = h->conv_terms;
         e.bias = bias;
         REQUIRE(conv_x3_forward_op(s, r, op, w, e), "bench layer 5: launch not covered");
       } else {

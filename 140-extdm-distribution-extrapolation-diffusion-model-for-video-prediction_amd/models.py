@@ -96,7 +96,9 @@ class Unet3D(nn.Module):
         self._native = None
         self._native_version = None
         self._extra_state = {}
-        self.precision = None  # conv arithmetic ('fp32' | 'f16x3'); None = _lib.DEFAULT_PRECISION
+        # arithmetic of the native handle, a key of _lib.PRECISIONS ('fp32' | 'f16x3' | 'bf16_attn' |
+        # 'f16_conv' | 'f16'); None = _lib.DEFAULT_PRECISION. Not a parameter or buffer: never in state_dict
+        self.precision = None
 
     # -- native handle management --------------------------------------------
     def _state_version(self):

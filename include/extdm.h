@@ -82,8 +82,16 @@ enum { EXTDM_SAMPLER_DDPM = 0, EXTDM_SAMPLER_DDIM = 1, EXTDM_SAMPLER_DPMPP = 2 }
  *          window and temporal layers on bf16 MFMA (v_mfma_f32_32x32x16_bf16, fp32
  *          accumulate; q, k, probabilities and v rounded to bf16), the configuration
  *          BASELINE names for UCF-101 256. Not fp32-faithful: tests/test_gpu_bf16_attn.py
- *          states its tolerance against the fp32 reference. */
-enum { EXTDM_PRECISION_FP32 = 0, EXTDM_PRECISION_F16X3 = 1, EXTDM_PRECISION_BF16_ATTN = 2 };
+ *          states its tolerance against the fp32 reference.
+ *   F16_CONV   F16X3 with ONE fp16 MFMA per product (hi(a) * hi(b), fp32 accumulate) in the
+ *          convolutions of the denoiser forward (extdm_unet_forward, the forward inside
+ *          extdm_sample and extdm_p_losses): both conv operands rounded to fp16. Attention,
+ *          norms and the sampler as in F16X3; every other entry point of the handle (the LFAE
+ *          encoder calls, extdm_decode, extdm_attn_layer) runs F16X3 bit for bit. The range
+ *          flag works as in F16X3. Not fp32-faithful: tests/test_gpu_f16_modes.py.
+ *   F16    F16_CONV plus the attention routing of BF16_ATTN: the fast inference mode. */
+enum { EXTDM_PRECISION_FP32 = 0, EXTDM_PRECISION_F16X3 = 1, EXTDM_PRECISION_BF16_ATTN = 2,
+       EXTDM_PRECISION_F16_CONV = 3, EXTDM_PRECISION_F16 = 4 };
 
 typedef struct ExtdmConfig {
   int arch;            /* EXTDM_ARCH_* */
@@ -319,7 +327,7 @@ int extdm_fvd_load_weight(ExtdmFvdHandle* h, const char* name, const void* host_
  * error): EXTDM_PRECISION_F16X3 (the default) or EXTDM_PRECISION_FP32, the exact-fp32 kernels on
  * v_mfma_f32_32x32x2_f32. finalize packs the chosen route's weights only. An FP32 handle never
  * narrows an operand: its range flag stays 0 and extdm_fvd_features never raises the fp16 range
- * error. EXTDM_PRECISION_BF16_ATTN is an error. */
+ * error. EXTDM_PRECISION_BF16_ATTN, _F16_CONV and _F16 are errors (denoiser modes). */
 int extdm_fvd_set_precision(ExtdmFvdHandle* h, int mode);
 int extdm_fvd_finalize(ExtdmFvdHandle* h);
 
